@@ -291,7 +291,7 @@ def extra_uniform(scale, edge_factor, seed, local_rank, rank, iters=10):
 def sgd_sampled_rows_check(g, nv, src, dst, val, lat0, lat1, users, items, K, lam, step, nsample, dev):
     """One ALL_EDGES SGD iteration recomputed for `nsample` user rows and `nsample` item rows from the same initial
     state, independently of the kernels (torch elementwise ops only, nothing shared with the library or the oracle),
-    with the reference's formulas AND evaluation order (/root/reference src/SGD.cpp:77-120: sequential K-term dot,
+    with the reference's formulas AND evaluation order (the reference's src/SGD.cpp:77-120: sequential K-term dot,
     error = rating - estimate, res = message * error; include/GMDP/singlenode/spmspv3.h:38-90: a row's results
     folded one by one in ascending NATIVE column order, the first one assigned; apply: lv += step * (-lambda * lv +
     sum)).  Every op is a separate IEEE fp32 multiply or add, so the comparison is expected to be bit-exact; the
@@ -437,6 +437,39 @@ def extra_sgd(users, items, per_user, iters, local_rank, rank):
             "rows_ok": bool(checked >= 2 * nsample and worst <= 1e-6 and exact == checked)}
 
 
+DUMP_SAMPLE = 1 << 21  # vertices written by --dump-outputs: 2^21 x (8 + 4 + 8) B = 40 MB at most
+DUMP_SEED = 20250101
+
+
+def dump_outputs(outdir, g, st, nv, rank, world, dev, on_host):
+    """--dump-outputs: what a caller of the timed path receives (Graph.pagerank: pagerank float32 and out-degree per vertex,
+    vertex order), for every vertex up to DUMP_SAMPLE vertices, else for a fixed seeded sample of vertex ids.  Sharded runs
+    fold the shards' rows onto rank 0, which writes the files.  Collective: every rank calls it."""
+    from graphmat_amd import api
+    if nv <= DUMP_SAMPLE:
+        idx = np.arange(nv, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, nv, DUMP_SAMPLE, dtype=np.int64))
+    don, _ = g.maps_to_host()
+    slots = torch.from_numpy(don[api.native_index(nv, g.nparts)[idx]].astype(np.int64)).to(dev)
+    del don
+    mine = (slots >= g.row_lo) & (slots < g.row_hi)
+    vals = torch.zeros((idx.size, 2), dtype=torch.int32, device=dev)
+    vals[mine] = st[slots[mine] - g.row_lo]
+    if world > 1:  # every vertex is owned by one shard, the others add zeros
+        import torch.distributed as dist
+        vals = vals.cpu() if on_host else vals
+        dist.all_reduce(vals, op=dist.ReduceOp.SUM)
+    if rank != 0:
+        return
+    vals = vals.cpu()
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "vertex.npy"), (idx + 1).astype(np.float64))
+    np.save(os.path.join(outdir, "pagerank.npy"), vals[:, 0].contiguous().view(torch.float32).numpy())
+    np.save(os.path.join(outdir, "out_degree.npy"), vals[:, 1].numpy().astype(np.float64))
+    log(rank, "outputs of the last timed step (%d of %d vertices) written to %s" % (idx.size, nv, outdir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -464,7 +497,12 @@ def main():
     ap.add_argument("--graph", choices=("rmat", "uniform", "rmat-scrambled"), default="rmat", help="rmat = the metric's input; uniform = every vertex with edge-factor out-edges to uniformly drawn destinations (the reference's test/generator.h:73-105 shape): policy robustness runs")
     ap.add_argument("--lib-option", action="append", default=[], metavar="KEY=VALUE", help="gm_set_option(KEY, VALUE) before the graph is built (experiments)")
     ap.add_argument("--debug-flags", type=int, default=0, help="ablation only (results become invalid): 1 skip fold, 2 skip gathers")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (vertex ids, pagerank, out_degree; "
+                         "a fixed seeded sample of %d vertices on larger graphs)" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -726,17 +764,20 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    g.run_pagerank(st, args.steps)
+    steps_done = g.run_pagerank(st, args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    assert steps_done == args.steps, "timed %d PageRank steps instead of %d" % (steps_done, args.steps)
     stats = g.last_stats()
     L.gm_debug_counters(cnt64)
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, st, nv, rank, world, dev, backend != "nccl")
     # N > 1 diagnostics (after the timed region, not part of `value`): the same schedule once more with an exchange that
     # moves NOTHING -- what the shards' kernels alone take (results are garbage, a scratch state is used) -- so that
     # exchange_ms_exposed = measured iteration - compute-only iteration is what the collectives add on the critical

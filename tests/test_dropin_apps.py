@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_APPS = os.path.join(ROOT, "build", "ref_apps")
+from oracle.ref_apps import OUT as REF_APPS  # noqa: E402
 OWN_APPS = os.path.join(ROOT, "build", "apps")
 
 
@@ -24,7 +24,8 @@ def test_apps_compile_for_gfx950():
     import build_apps
     built = build_apps.build()
     assert any(p.endswith("label_propagation") for p in built) and any(p.endswith("bfs_bottom_up") for p in built)
-    if os.path.isdir("/root/reference/src"):
+    from oracle import ref_apps
+    if ref_apps.present():
         for app in ("PageRank", "BFS", "SGD", "SSSP"):
             assert os.path.exists(os.path.join(REF_APPS, app))
 
@@ -118,7 +119,7 @@ def test_own_generic_program_label_propagation(golden_dir, tmp_path):
 
 
 @pytest.mark.gpu
-def test_own_bfs_with_row_filter_trait(golden_dir, ref):
+def test_own_bfs_with_row_filter_trait(golden_dir, ref, tmp_path):
     """apps/bfs_bottom_up.cpp: a user-written BFS whose only extras are two traits: program_row_filter (bottom-up
     levels) and program_traits::reduce = REDUCE_LAST (the declared reduction strategy).  Golden depths/parents of G2, and the oracle
     on an RMAT graph large enough to have row-blocks, wave rows and top-down steps."""
@@ -133,7 +134,7 @@ def test_own_bfs_with_row_filter_trait(golden_dir, ref):
     assert [int(r[1]) for r in rows] == g2["depth"] and [int(r[2]) for r in rows] == g2["parent"]
     assert "Completed %d iterations" % g2["iterations"] in text
     nv, s, d, v = gen.rmat_edges(14, 16, seed=5)
-    path = "/tmp/bfs_bottom_up_rmat14.bin.mtx"
+    path = str(tmp_path / "bfs_bottom_up_rmat14.bin.mtx")
     write_mtx_bin(path, nv, s, d, v)
     text = _run(exe, path, 3)
     got = {int(a): (int(b), int(c)) for a, b, c in re.findall(r"^vertex (\d+) depth (\d+) parent (-?\d+)$", text, flags=re.M)}
@@ -146,7 +147,7 @@ def test_own_bfs_with_row_filter_trait(golden_dir, ref):
 
 
 @pytest.mark.gpu
-def test_untraited_programs_on_a_graph_with_giant_rows():
+def test_untraited_programs_on_a_graph_with_giant_rows(tmp_path):
     """apps/untraited_programs.cpp: what an UNCHANGED application gets by default -- programs without program_traits, i.e. the
     ordered fold for every reduce_function -- on RMAT-16 (hub rows of 13 K in-edges: giant rows, whose ordered fold runs in
     two passes, k_giant_terms + k_giant_fold_ordered): BFS with 8-byte a = b messages over a sparse message vector, SSSP with a
@@ -158,7 +159,7 @@ def test_untraited_programs_on_a_graph_with_giant_rows():
     ob.build()
     exe = _need(os.path.join(OWN_APPS, "untraited_programs"))
     nv, s, d, v = gen.rmat_edges(16, 16, seed=11, weights="hash")
-    path = "/tmp/untraited_rmat16.bin.mtx"
+    path = str(tmp_path / "untraited_rmat16.bin.mtx")
     write_mtx_bin(path, nv, s, d, v)
     text = _run(exe, path, 5, 6)
     og = ob.OracleGraph(nv, s, d, v, ref_threads=1)

@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_APPS = os.path.join(ROOT, "build", "ref_apps")
+from oracle.ref_apps import OUT as REF_APPS  # noqa: E402
 
 
 def _launch(exe, args, nranks, tmp_path, transport):

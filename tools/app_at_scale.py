@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Run the reference's UNCHANGED application binaries (build/ref_apps) on a synthetic RMAT file.
+"""Run the reference's UNCHANGED application binaries (oracle/_ref, oracle/ref_apps.py) on a synthetic RMAT file.
 Usage: python tools/app_at_scale.py <scale> [uniform]   (uniform: 2^scale vertices x 16 uniformly drawn out-edges, values 1: a graph without skew; PageRank only)"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from graphmat_amd import api
 from graphmat_amd.mtx import write_mtx_bin
+from oracle import ref_apps
 scale = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 uniform = len(sys.argv) > 2 and sys.argv[2] == "uniform"
 if uniform:
@@ -17,7 +18,7 @@ else:
 path = "/tmp/%s%d.bin.mtx" % ("uniform" if uniform else "rmat", scale)
 write_mtx_bin(path, nv, s.cpu().numpy(), d.cpu().numpy(), v.cpu().numpy())
 for app, args in ((("PageRank", []),) if uniform else (("PageRank", []), ("BFS", ["1"]), ("SSSP", ["1"]))):
-    exe = os.path.join(ROOT, "build", "ref_apps", app)
+    exe = ref_apps.path(app)
     if not os.path.exists(exe):
         print(app, "binary not prebuilt"); continue
     t0 = time.time()

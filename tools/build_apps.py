@@ -3,16 +3,15 @@
 
   * apps/*.cpp            -- this project's own example programs (always)
   * <reference>/src/{PageRank,BFS,SGD,SSSP,IncrementalPageRank,TopologicalSort,DeltaStepping}.cpp -- the reference's UNCHANGED application
-    sources, compiled where they lie when the reference tree is present (build container
-    only).  Outputs go to build/ref_apps/ (git-ignored; they travel to the GPU box like any
-    other built artefact).  Nothing from the reference is copied into the repository.
+    sources, compiled where they lie when the reference tree is present, by the recipe of oracle/ref_apps.py.  Outputs go
+    to oracle/_ref/ (git-ignored; they travel with the tree to where the tests run).  Nothing from the reference is copied
+    into the repository.
 """
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("GRAPHMAT_REFERENCE", "/root/reference")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "--hipstdpar", "-ffp-contract=off", "-w", "-DGRAPHMAT_NO_MPI",
          "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "graphmat_amd"), "-lgraphmat_hip"]
@@ -56,13 +55,10 @@ def build(verbose=False, jobs=None):
     for f in sorted(os.listdir(appdir)):
         if f.endswith(".cpp"):
             work.append((os.path.join(appdir, f), os.path.join(outdir, f[:-4])))
-    if os.path.isdir(os.path.join(REF, "src")):
-        outdir = os.path.join(ROOT, "build", "ref_apps")
-        os.makedirs(outdir, exist_ok=True)
-        for app in ("PageRank", "BFS", "SGD", "SSSP", "IncrementalPageRank", "TopologicalSort", "DeltaStepping"):
-            work.append((os.path.join(REF, "src", app + ".cpp"), os.path.join(outdir, app)))
-        # the reference's own tracing build (-D__TIMING, its Makefile's `timing` flavour): per-iteration lines
-        work.append((os.path.join(REF, "src", "PageRank.cpp"), os.path.join(outdir, "PageRank__TIMING"), ("-D__TIMING",)))
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle import ref_apps
+    work += ref_apps.work()
     jobs = jobs or max(1, min(6, (os.cpu_count() or 2) - 1))
     with ThreadPoolExecutor(max_workers=jobs) as pool:
         list(pool.map(lambda w: _compile(w[0], w[1], "$ORIGIN/../../graphmat_amd", w[2] if len(w) > 2 else ()), work))
