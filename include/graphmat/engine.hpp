@@ -980,6 +980,9 @@ class Run {
     GM_HIP_OK(hipStreamSynchronize(s));
     gm_graph_note_set(g, 3, (int64_t)sparse_sweeps);
     gm_graph_note_set(g, 4, (int64_t)short_folds);
+    gm_graph_note_set(g, 5, (int64_t)((unsigned long long)step_count[STEP_PULL] | (unsigned long long)step_count[STEP_LIST] << 16 |
+                                      (unsigned long long)step_count[STEP_BITS] << 32 | (unsigned long long)step_count[STEP_DENSE_PUSH] << 48));
+    gm_graph_note_set(g, 6, (int64_t)step_kinds);
     tick("loop done", it);
     aux.finish();
     st.iterations = it;
@@ -1634,6 +1637,14 @@ class Run {
   bool said_blocked = false, said_sparse_sweep = false, said_short_fold = false;
   int sparse_sweeps = 0;  // multiplies of this run that took a sparse x through the sweep (note 3 of the graph: tests read it)
   int short_folds = 0;    // multiplies of this run whose short rows were folded from the sweep's products stream (note 4)
+  // which step every iteration of run_loop took (graphmat_hip.h: notes 5 and 6 of the graph: tests compare them with the rule restated on the host)
+  enum { STEP_PULL = 0, STEP_LIST = 1, STEP_BITS = 2, STEP_DENSE_PUSH = 3 };
+  unsigned int step_count[4] = {0, 0, 0, 0};  // iterations per kind, saturating at 65535
+  unsigned long long step_kinds = 0;          // the kinds of the first 32 iterations, two bits each
+  void count_step(int it, int kind) {
+    if (step_count[kind] < 0xffffu) step_count[kind]++;
+    if (it < 32) step_kinds |= (unsigned long long)kind << (2 * it);
+  }
   bool blocked_usable(int acc, gm_blocked_t* bl) {
     if constexpr (sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<T>::value && std::is_trivially_copyable<U>::value) {
       if (use_vp || xq == nullptr || xb != nullptr || d_want != nullptr || program_row_filter<P>::enabled || (acc & dev::ACC_READ_PREV)) return false;
@@ -1935,6 +1946,12 @@ class Run {
       // ... and an active set too large to list whose vertices own only a few out-edges each bids straight from the bitmap
       const bool bits_push = can_push && !push && rk == REDUCE_LAST && frontier_v > (unsigned long long)dev::kSparseListCap &&
                              frontier_e <= (unsigned long long)opt.bits_step_edges && frontier_maxdeg <= 64ull;
+      const int step_kind = bits_push ? STEP_BITS : sparse ? STEP_LIST : dense_push ? STEP_DENSE_PUSH : STEP_PULL;
+      count_step(it, step_kind);
+      if (verbose && can_push) {
+        static const char* const step_names[4] = {"pull", "list push", "bits push", "pull with dense push"};
+        printf("GraphMat(HIP):   step: %s\n", step_names[step_kind]);
+      }
       if (bits_push) step_bits_push(pa);
       else if (sparse) step_list_push(pa);
       else step_pull(pa, it, xsp, dense_push, want_stats);

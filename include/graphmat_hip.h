@@ -521,7 +521,13 @@ int gm_graph_split(const gm_graph_t* g, int direction, int head_permille, int32_
                    int32_t* mid_split);
 /* a few integers the header layer may park on a graph between runs (slot in [0, GM_NOTE_SLOTS));
  * get returns GM_ERR_INVALID while a slot has never been set; rebuilding the adjacency
- * (gm_graph_relayout_like) clears them */
+ * (gm_graph_relayout_like) clears them.
+ * Slots 5 and 6 are written at the end of every run: which step each iteration of the plain loop
+ * (engine.hpp: run_loop) took.  Kinds: 0 pull, 1 list push, 2 bits push, 3 pull with dense push.
+ *   5: iterations per kind, 16 bits each, saturating: pull | list << 16 | bits << 32 | dense_push << 48
+ *   6: the kinds of the first 32 iterations, two bits each: iteration i in bits 2i..2i+1
+ * A run that does not go through that loop (the fixed-count two-stage and sharded swept schedules)
+ * leaves both at 0. */
 #define GM_NOTE_SLOTS 8
 int gm_graph_note_set(gm_graph_t* g, int slot, int64_t value);
 int gm_graph_note_get(const gm_graph_t* g, int slot, int64_t* value);

@@ -129,14 +129,15 @@ def test_own_bfs_with_row_filter_trait(golden_dir, ref, tmp_path):
     ob.build()
     exe = _need(os.path.join(OWN_APPS, "bfs_bottom_up"))
     g2 = ref["G2_bfs_test_bin_mtx"]
-    text = _run(exe, os.path.join(golden_dir, g2["file"]), g2["source"])
+    one = {"GRAPHMAT_NUM_THREADS": "1"}  # the layout parameter of the golden files and of the oracle below (else: OMP_NUM_THREADS)
+    text = _run(exe, os.path.join(golden_dir, g2["file"]), g2["source"], env=one)
     rows = re.findall(r"^vertex (\d+) depth (\d+) parent (-?\d+)$", text, flags=re.M)
     assert [int(r[1]) for r in rows] == g2["depth"] and [int(r[2]) for r in rows] == g2["parent"]
     assert "Completed %d iterations" % g2["iterations"] in text
     nv, s, d, v = gen.rmat_edges(14, 16, seed=5)
     path = str(tmp_path / "bfs_bottom_up_rmat14.bin.mtx")
     write_mtx_bin(path, nv, s, d, v)
-    text = _run(exe, path, 3)
+    text = _run(exe, path, 3, env=one)
     got = {int(a): (int(b), int(c)) for a, b, c in re.findall(r"^vertex (\d+) depth (\d+) parent (-?\d+)$", text, flags=re.M)}
     od, op, oit, _ = ob.OracleGraph(nv, s, d, v, ref_threads=1).bfs(3)
     reached = np.where(od != 0xFFFFFFFF)[0]
@@ -161,7 +162,8 @@ def test_untraited_programs_on_a_graph_with_giant_rows(tmp_path):
     nv, s, d, v = gen.rmat_edges(16, 16, seed=11, weights="hash")
     path = str(tmp_path / "untraited_rmat16.bin.mtx")
     write_mtx_bin(path, nv, s, d, v)
-    text = _run(exe, path, 5, 6)
+    one = {"GRAPHMAT_NUM_THREADS": "1"}  # the layout parameter of the oracle below (else: OMP_NUM_THREADS)
+    text = _run(exe, path, 5, 6, env=one)
     og = ob.OracleGraph(nv, s, d, v, ref_threads=1)
     od, op, oit, _ = og.bfs(5)
     got = {int(a): (int(b), int(c)) for a, b, c in re.findall(r"^bfs (\d+) (\d+) (-?\d+)$", text, flags=re.M)}
@@ -186,15 +188,15 @@ def test_untraited_programs_on_a_graph_with_giant_rows(tmp_path):
     # The GUIDED PULL (engine.hpp; round 6): on large graphs the levels of an undeclared ACTIVE_ONLY program whose active set owns few
     # out-edges only fold the rows that set reaches (marked first, then the same kernels in the same order).  Forced here on the small
     # graph (guided_pull = 2): every line of the output must be the same, and the path must really have been taken.
-    text2 = _run(exe, path, 5, 6, env={"GRAPHMAT_OPTIONS": "guided_pull=2", "GRAPHMAT_VERBOSE": "1"})
+    text2 = _run(exe, path, 5, 6, env=dict(one, GRAPHMAT_OPTIONS="guided_pull=2", GRAPHMAT_VERBOSE="1"))
     assert "guided pull: " in text2 and text2.count("   guided pull:") >= 4, text2[:2000]
     keep = lambda t: sorted(l for l in t.splitlines() if re.match(r"^(bfs|sssp|pr) ", l))
     assert keep(text2) == keep(text)
-    text0 = _run(exe, path, 5, 6, env={"GRAPHMAT_OPTIONS": "guided_pull=0", "GRAPHMAT_VERBOSE": "1"})
+    text0 = _run(exe, path, 5, 6, env=dict(one, GRAPHMAT_OPTIONS="guided_pull=0", GRAPHMAT_VERBOSE="1"))
     assert "guided pull" not in text0 and keep(text0) == keep(text)
     # ... and on a graph with slices (forced here: GRAPHMAT_COL_TILES) the undeclared SSSP's sparse message vector goes through the sweep
     # (k_spmv_sell_sparse: 4-byte messages, int edge values in the structure, the program's own min as an ordered fold): same lines again
-    text3 = _run(exe, path, 5, 6, env={"GRAPHMAT_COL_TILES": "3", "GRAPHMAT_VERBOSE": "1", "GRAPHMAT_OPTIONS": "sweep_form=64"})
+    text3 = _run(exe, path, 5, 6, env=dict(one, GRAPHMAT_COL_TILES="3", GRAPHMAT_VERBOSE="1", GRAPHMAT_OPTIONS="sweep_form=64"))
     assert "sparse message vector through the sweep" in text3 and keep(text3) == keep(text)
 
 
@@ -439,3 +441,123 @@ def test_undeclared_float_sums_speculated_and_proven():
     text = _run(_need(os.path.join(OWN_APPS, "speculated_float_sum")))
     assert "SPECULATED PASS" in text, text[-2000:]
 
+
+
+# ---- the same applications with the step choice of the iteration loop forced (engine.hpp: run_loop) ------------------------
+# GRAPHMAT_OPTIONS of three regimes: every level a pull; a list-based top-down step wherever one is possible; the bids of a
+# top-down step resolved by a pass over all vertices wherever that is possible (graphmat_hip.h: no option changes a result)
+FORCED_STEPS = {
+    "pull only": "push_edge_permille=0",
+    "list whenever possible": "push_edge_permille=1000,sparse_step_edges=2147483647",
+    "dense push whenever possible": "push_edge_permille=1000,sparse_step_edges=0",
+}
+
+
+def _result_lines(text, pattern):
+    return [l for l in text.splitlines() if re.match(pattern, l)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", sorted(FORCED_STEPS))
+def test_last_writer_program_under_forced_steps(regime):
+    """apps/last_writer.cpp rewrites the senders in the step they send in: whichever step the loop is made to take, the
+    messages are those of BEFORE the step and the result is the host restatement's.  The program declares no reduction
+    strategy, so as it stands it gets the ordered fold and only ever pulls; with GRAPHMAT_TRUST_PROBE=1 its a = b
+    reduce_function is recognised (strategy 2) and the forced regimes really take the top-down steps, which the verbose
+    lines of the loop must show."""
+    exe = _need(os.path.join(OWN_APPS, "last_writer"))
+    pat = r"^\d+ mismatches; \d+ iterations on the device, \d+ on the host$"
+    base = _run(exe)
+    assert "LASTWRITER PASS" in base and len(_result_lines(base, pat)) == 1, base[-1500:]
+    for probe in ({}, {"GRAPHMAT_TRUST_PROBE": "1"}):
+        text = _run(exe, env=dict(probe, GRAPHMAT_OPTIONS=FORCED_STEPS[regime], GRAPHMAT_VERBOSE="1"))
+        assert "ignoring" not in text, text[-1500:]
+        assert "LASTWRITER PASS" in text, text[-1500:]
+        assert _result_lines(text, pat) == _result_lines(base, pat)
+        steps = re.findall(r"^GraphMat\(HIP\):   step: (.*)$", text, flags=re.M)
+        if not probe:
+            assert "reduce strategy 0" in text and steps == []
+            continue
+        assert "reduce strategy 2" in text and len(steps) == int(_result_lines(base, pat)[0].split()[2])
+        if regime == "pull only":
+            assert set(steps) == {"pull"}
+        elif regime == "list whenever possible":
+            assert set(steps) == {"list push"}
+        else:  # (an active set without out-edges is a list step under any setting: nothing to bid for)
+            assert steps.count("pull with dense push") >= 3 and set(steps) <= {"pull with dense push", "list push"}
+
+
+STEP_LINE = {0: "pull", 1: "list push", 2: "bits push", 3: "pull with dense push"}  # GRAPHMAT_VERBOSE=1, codes of graphmat_hip.h notes 5 / 6
+
+
+def _predicted_steps(regime, stats, nnz, reduce_last):
+    """the loop's rule (tests/test_gpu_frontier_steps.py: predict_kinds) for a GRAPHMAT_OPTIONS string"""
+    from tests.test_gpu_frontier_steps import predict_kinds
+    opts = {k: int(v) for k, v in (kv.split("=") for kv in FORCED_STEPS[regime].split(","))}
+    return [STEP_LINE[k] for k in predict_kinds(stats, nnz, opts, reduce_last)]
+
+
+def _forced_runs(exe, args, regime, pat, strategy, stats, predicted):
+    """the application as it stands (no declared strategy: ordered fold, pulls only) and with its reduce_function probed
+    (GRAPHMAT_TRUST_PROBE=1), where the top-down steps are open to it: the same result lines every time.  In the probed run
+    the loop's "active set" line of every iteration must carry the predicted (vertices, out-edges, max out-degree) -- the
+    statistics the kernels of the forced regime counted, from which the loop chooses.  The reference's applications are
+    prebuilt and may come from a build of other sources than this checkout's, so the "step" lines, which only newer
+    builds print, are compared with the prediction where the binary prints them (apps/last_writer.cpp, always built with
+    the checkout, is held to them above)."""
+    base = _result_lines(_run(exe, *args), pat)
+    for probe in ({}, {"GRAPHMAT_TRUST_PROBE": "1"}):
+        text = _run(exe, *args, env=dict(probe, GRAPHMAT_OPTIONS=FORCED_STEPS[regime], GRAPHMAT_VERBOSE="1"))
+        assert "ignoring" not in text, text[-1500:]
+        assert _result_lines(text, pat) == base
+        sets = [tuple(int(x) for x in m) for m in
+                re.findall(r"^GraphMat\(HIP\):   active set: (\d+) vertices, (\d+) out-edges \(max (\d+)\)$", text, flags=re.M)]
+        steps = re.findall(r"^GraphMat\(HIP\):   step: (.*)$", text, flags=re.M)
+        if probe:
+            assert "reduce strategy %d" % strategy in text
+            assert sets == [tuple(s) for s in stats], (sets, stats)
+            assert steps == predicted or steps == [], (steps, predicted)
+        else:
+            assert "reduce strategy 0" in text and sets == [] and steps == []
+    return base
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", sorted(FORCED_STEPS))
+def test_reference_bfs_app_under_forced_steps(golden_dir, ref, regime):
+    from graphmat_amd.mtx import read_mtx_bin
+    from oracle import binding as ob
+    from tests.test_gpu_frontier_steps import bfs_level_stats
+    exe = _need(os.path.join(REF_APPS, "BFS"))
+    pat = r"^(Depth \d+ : (\d+ parent: -?\d+|INF ?)|Completed \d+ iterations.*|Reachable vertices = \d+.*)$"
+    for key in ("G2_bfs_test_bin_mtx", "G2_bfs_2_10_upper_triangle"):
+        g2 = ref[key]
+        path = os.path.join(golden_dir, g2["file"])
+        nv, s, d, v = read_mtx_bin(path)
+        depth, _, it, _ = ob.OracleGraph(nv, s, d, v, 1).bfs(g2["source"])
+        stats = bfs_level_stats(depth, it, np.bincount(s - 1, minlength=nv))
+        predicted = _predicted_steps(regime, stats, len(s), True)
+        assert len(predicted) == g2["iterations"] and set(predicted) == {STEP_LINE[{"p": 0, "l": 1, "d": 3}[regime[0]]]}
+        base = _forced_runs(exe, (path, g2["source"]), regime, pat, 2, stats, predicted)
+        assert "Completed %d iterations " % g2["iterations"] in base and "Reachable vertices = %d " % g2["reachable"] in base
+        assert len([l for l in base if l.startswith("Depth ")]) >= 8
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", sorted(FORCED_STEPS))
+def test_reference_sssp_app_under_forced_steps(golden_dir, regime):
+    from graphmat_amd.mtx import read_mtx_bin
+    from oracle import binding as ob
+    from tests.test_gpu_frontier_steps import sssp_rounds
+    exe = _need(os.path.join(REF_APPS, "SSSP"))
+    pat = r"^(\d+ : distance = (\d+|INF)|Completed \d+ iterations.*|Reachable vertices = \d+.*)$"
+    path = os.path.join(golden_dir, "2_10_upper_triangle.bin.mtx")
+    nv, s, d, v = read_mtx_bin(path)
+    dist, stats = sssp_rounds(nv, s, d, v, 1)
+    odist, oit = ob.OracleGraph(nv, s, d, v, 1).sssp(1)
+    assert np.array_equal(dist, odist) and oit == len(stats)
+    predicted = _predicted_steps(regime, stats, len(s), False)  # (min is commutative: list steps or pulls, no dense push)
+    assert set(predicted) == {"list push" if regime[0] == "l" else "pull"}
+    base = _forced_runs(exe, (path, 1), regime, pat, 1, stats, predicted)
+    assert "Completed %d iterations " % len(stats) in base and "Reachable vertices = %d " % int((dist != 0xFFFFFFFF).sum()) in base
+    assert len(base) == 27
