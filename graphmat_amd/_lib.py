@@ -72,6 +72,11 @@ class EngineOptions(C.Structure):
                                          "sparse_step_edges", "iteration_trace", "ablate_cold_from", "ablate_cold_short", "two_stage_head_permille", "giant_stream", "sweep_form", "blocked_form", "guided_pull")] + [("reserved_", C.c_int32 * 12)]
 
 
+class Lda20(C.Structure):
+    """gm_lda20_t: the reference's LatentVector<20> (176 bytes)"""
+    _fields_ = [("N", C.c_double * 20), ("type", C.c_char), ("token_loglik", C.c_double)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int))
 
 # name -> (restype, argtypes); every symbol include/graphmat_hip.h declares
@@ -127,6 +132,11 @@ SIGNATURES = {
     "gm_run_rmse": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "gm_run_sgd_bipartite": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                        C.POINTER(C.c_int), _P]),
+    "gm_run_lda_init": (C.c_int, [_P, _P, C.c_int, _P]),
+    "gm_lda_global_n": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "gm_run_lda": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "gm_run_lda_loglik": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), _P]),
+    "gm_lda_edge_init": (C.c_int, [C.c_int, C.c_int, _P]),
     "gm_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "gm_graph_engine_options": (C.c_int, [_P, C.POINTER(EngineOptions)]),
     "gm_graph_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),

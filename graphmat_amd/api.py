@@ -18,6 +18,9 @@ from . import _lib
 from ._lib import GM_DIR_IN, GM_DIR_OUT, GM_LAYOUT_DEGREE, GM_LAYOUT_NATIVE, check
 
 MAX_DIST = 0xFFFFFFFF
+# gm_lda20_t (_lib.Lda20) as a numpy record
+LDA20_DTYPE = np.dtype({"names": ["N", "type", "token_loglik"], "formats": [("<f8", (20,)), "u1", "<f8"],
+                        "offsets": [0, 160, 168], "itemsize": 176})
 
 
 def native_index(nv, nparts):
@@ -267,6 +270,50 @@ class Graph:
         check(fn(st.data_ptr() + K * st.element_size(), self.rows, K + 1, C.byref(out), _stream()))
         sq = self.to_vertex_order(st)[:, K].cpu().numpy()
         return out.value, sq
+
+    # ---- LDA (K = 20, fp64) ----------------------------------------------------------------
+    # A corpus: documents are vertices 1..ndoc, words the rest, edges document -> word carry token counts.
+    # States travel as [nv, 20] float64 arrays in vertex order; the 176-byte records of gm_lda20_t are built here.
+    def _lda_to_device(self, N, ndoc):
+        N = np.ascontiguousarray(N, np.float64)
+        assert N.shape == (self.nv, 20), "LDA state: [nv, 20] float64"
+        rec = np.zeros(self.nv, LDA20_DTYPE)
+        rec["N"] = N
+        rec["type"] = np.where(np.arange(self.nv) < ndoc, ord("d"), ord("w"))
+        st = torch.from_numpy(rec.view(np.float64).reshape(self.nv, 22))  # (moved as 22 doubles a record; no arithmetic touches them)
+        return self.to_device_order(st).contiguous()
+
+    def _lda_N(self, st):
+        return self.to_vertex_order(st)[:, :20].cpu().numpy()
+
+    def lda_init(self, ndoc):
+        """gm_run_lda_init from an all-zero state.  Returns N [nv, 20]; rows without edges are zeros."""
+        st = self._lda_to_device(np.zeros((self.nv, 20)), ndoc)
+        check(self.L.gm_run_lda_init(self.h, st.data_ptr(), 20, _stream()))
+        return self._lda_N(st)
+
+    def lda_global_n(self, N, ndoc):
+        """The sum of N over the word vertices, [20] (the library's fixed summation order)."""
+        st = self._lda_to_device(N, ndoc)
+        out = np.zeros(20, np.float64)
+        check(self.L.gm_lda_global_n(self.h, st.data_ptr(), 20, out.ctypes.data, _stream()))
+        return out
+
+    def lda(self, N, ndoc, nterms, alpha, eta, iterations):
+        """`iterations` LDA steps (vocab_size = nterms).  Returns (N', global_N of N', iterations_done)."""
+        st = self._lda_to_device(N, ndoc)
+        it = C.c_int(0)
+        gn = np.zeros(20, np.float64)
+        check(self.L.gm_run_lda(self.h, st.data_ptr(), 20, alpha, eta, float(nterms), iterations, C.byref(it), gn.ctypes.data,
+                                _stream()))
+        return self._lda_N(st), gn, it.value
+
+    def lda_loglik(self, N, ndoc, nterms, eta):
+        """Returns (total log-likelihood, token_loglik [nv]); documents receive nothing and stay 0."""
+        st = self._lda_to_device(N, ndoc)
+        out = C.c_double(0)
+        check(self.L.gm_run_lda_loglik(self.h, st.data_ptr(), 20, eta, nterms, C.byref(out), _stream()))
+        return out.value, self.to_vertex_order(st)[:, 21].cpu().numpy()
 
 
 _hip = None

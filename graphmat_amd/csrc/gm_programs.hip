@@ -15,13 +15,15 @@
 
 #include "GraphMatRuntime.h"
 #include "gm_internal.hpp"
+#include "gm_run_fixed.hpp"
 
 #define HD __host__ __device__
 
 namespace gm {
 
 extern int g_short_row, g_giant_row, g_rank_by, g_rank_cap, g_col_tiles, g_tile_min_row, g_long_mid, g_tile_balance, g_own_wave_row, g_sort_tile_lists, g_sweep_slices, g_sweep_acc_limit, g_sweep_long_limit, g_sweep_long_row, g_sweep_fold_share, g_sweep_border_factor, g_blocked_rows, g_sweep_waves, g_sweep_stream, g_sweep_stream_weight;
-static int g_force_ordered = 0;
+int g_force_ordered = 0;  // (read by gm_lda.hip as well)
+extern int g_lda_tile;
 
 // ---------------- PageRank (reference: src/PageRank.cpp:34-112) ----------------------------
 struct PRv : gm_pr_t {
@@ -672,45 +674,6 @@ static bool wide_path_ok(const gm_graph_t* g) {
          (whole || g->xfn != nullptr) && !g_force_ordered;
 }
 
-// run a program on caller-provided device state through the common engine
-template <class P, class V>
-int run_fixed(P& prog, gm_graph_t* g, V* d_vp, uint32_t* d_active, int iterations, int* iters_done, hipStream_t s) {
-  typedef typename GraphMat::detail::types_of<P>::type PT;
-  typedef typename PT::msg T;
-  typedef typename PT::red U;
-  if (!g || !d_vp) { set_error("gm_run_*: null graph or vertex state"); return GM_ERR_INVALID; }
-  const gm_graph_desc_t& d = g->desc;
-  const int rows = d.row_hi - d.row_lo;
-  const auto order = prog.getOrder();
-  if ((order != GraphMat::IN_EDGES && !g->out.present) || (order != GraphMat::OUT_EDGES && !g->in.present)) {
-    set_error("gm_run_*: graph was built without the adjacency direction this program needs");
-    return GM_ERR_INVALID;
-  }
-  void *p0, *p1, *p2, *p3, *p5;
-  int rc;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * sizeof(T) + 16, &p0))) return rc;
-  if ((rc = gm_graph_workspace(g, 2, ((size_t)(d.ndevice + 31) / 32 + 2) * 4, &p1))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)rows * sizeof(U) + 16, &p2))) return rc;
-  if ((rc = gm_graph_workspace(g, 4, ((size_t)(rows + 31) / 32 + 2) * 4, &p3))) return rc;
-  if (!d_active) {
-    const size_t nw = (size_t)(rows + 31) / 32;
-    if ((rc = gm_graph_workspace(g, 5, (nw + 2) * 4, &p5))) return rc;
-    d_active = (uint32_t*)p5;
-    hipLaunchKernelGGL(GraphMat::dev::k_fill_u32, dim3(GraphMat::detail::grid_for((int64_t)nw)),
-                       dim3(GraphMat::dev::kBlock), 0, s, d_active, (int64_t)nw, 0xffffffffu);
-    if (rows & 31) {
-      uint32_t tail = (1u << (rows & 31)) - 1u;
-      GM_TRY_HIP(hipMemcpyAsync(d_active + nw - 1, &tail, 4, hipMemcpyHostToDevice, s));
-      GM_TRY_HIP(hipStreamSynchronize(s));
-    }
-  }
-  int it = GraphMat::detail::run_on_device<P, T, U, V, int>(&prog, g, order, prog.getActivity(),
-                                                             prog.getProcessMessageRequiresVertexprop(), d_vp, d_active,
-                                                             (T*)p0, (uint32_t*)p1, (U*)p2, (uint32_t*)p3, iterations, s);
-  if (iters_done) *iters_done = it;
-  return GM_OK;
-}
-
 // The HIP runtime resolves a code object's kernel table at the first launch of one of its
 // kernels (milliseconds for this translation unit's template instantiations): do it when the
 // first graph is created, not inside the first run.
@@ -825,6 +788,7 @@ int gm_reset_options(void) {
   gm::engine_defaults() = gm::engine_documented_defaults();
   gm::g_force_ordered = 0;
   gm::g_sgd_mfma = 0;
+  gm::g_lda_tile = GM_LDA_TILE_DEFAULT;
   gm::g_short_row = GM_SHORT_ROW;
   gm::g_giant_row = 0;
   gm::g_rank_cap = 0;
@@ -855,6 +819,7 @@ int gm_set_option(const char* key, int value) {
   }
   if (key && !strcmp(key, "force_ordered")) { gm::g_force_ordered = value; return GM_OK; }
   if (key && !strcmp(key, "sgd_mfma") && (value == 0 || value == 1)) { gm::g_sgd_mfma = value; return GM_OK; }
+  if (key && !strcmp(key, "lda_tile") && (value == 16 || value == 32 || value == 64)) { gm::g_lda_tile = value; return GM_OK; }
   if (key && !strcmp(key, "short_row") && value >= 1 && value <= GM_BLOCK_NNZ) { gm::g_short_row = value; return GM_OK; }
   if (key && !strcmp(key, "giant_row") && value >= 64) { gm::g_giant_row = value; return GM_OK; }
   if (key && !strcmp(key, "rank_cap") && value >= 0) { gm::g_rank_cap = value; return GM_OK; }

@@ -2434,7 +2434,7 @@ __device__ __forceinline__ int lower_piece(const int32_t* __restrict__ gchunk_ro
 // ---- the sub-pieces' maps of a pass (float sums over a dense x; see gchunk_state) ------------------------------------------------------
 // one workgroup per 4096-product piece, a sub-piece = 32 consecutive threads x 16 consecutive products
 // (1) the products of every sub-piece added up in double
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_giant_sums(gm_csr_t A, const float* __restrict__ terms, gchunk_state* __restrict__ state) {
   constexpr int PER = GM_GIANT_CHUNK / kBlock, kSubs = GM_GIANT_CHUNK / kGiantSub, kLanesPerSub = kGiantSub / PER;
   static_assert(kLanesPerSub == 32 && kSubs * kLanesPerSub == kBlock, "a sub-piece is half a wave's products");
@@ -2474,7 +2474,7 @@ __device__ __forceinline__ int f32_binade_of(double d) {
 // (3) the map of every sub-piece whose S is expected to start and end in the same binade of a positive normal number.  The workgroup of a
 // piece adds up the sums of the row's EARLIER sub-pieces itself (the hub row's last piece: 1664 doubles, seven loads per thread) instead of
 // waiting for a scan kernel in between: a separate one-wave-per-row scan took 55 us for the hub row.
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_giant_maps(gm_csr_t A, const float* __restrict__ terms, gchunk_state* __restrict__ state, const float* __restrict__ y, const uint32_t* __restrict__ ybits,
              int accumulate) {
   constexpr int PER = GM_GIANT_CHUNK / kBlock, kSubs = GM_GIANT_CHUNK / kGiantSub, kLanesPerSub = kGiantSub / PER;
@@ -3271,7 +3271,7 @@ k_giant_verify_chunks_any(ProgArg<P> pa, gm_csr_t A, const V* __restrict__ vp, c
 
 // frontier statistics: number of active vertices, of their out-edges, and the largest out-degree.
 // Grid-stride with one set of atomics per workgroup (launch <= 2048 workgroups).
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_frontier_stats(const uint32_t* __restrict__ active, const int64_t* __restrict__ src_rowptr, int n,
                  unsigned long long* __restrict__ stats /* [0] vertices, [1] out-edges, [2] max out-degree */,
                  int32_t* __restrict__ list /* also list the active vertices while they are few, or null */,
@@ -3314,7 +3314,7 @@ k_frontier_stats(const uint32_t* __restrict__ active, const int64_t* __restrict_
 }
 
 // compact list of the active vertices (order irrelevant)
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_frontier_list(const uint32_t* __restrict__ active, int n, int32_t* __restrict__ list, unsigned int* __restrict__ count) {
   __shared__ int32_t s_lbuf[kListBuf];
   __shared__ unsigned int s_lfill[4];
@@ -3355,7 +3355,7 @@ __device__ __forceinline__ unsigned int block_scan_inclusive(unsigned int v, uns
   *total = all;
   return before + inc;
 }
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_piece_count(gm_csr_t S, const int32_t* __restrict__ list, int nlist, unsigned int* __restrict__ block_sum) {
   __shared__ unsigned int s_w[kBlock / 64];
   const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -3363,7 +3363,7 @@ k_piece_count(gm_csr_t S, const int32_t* __restrict__ list, int nlist, unsigned 
   (void)block_scan_inclusive(i < nlist ? pieces_of(S, list[i]) : 0u, s_w, &total);
   if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
 }
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_piece_block_scan(unsigned int* __restrict__ block_sum, int nblocks) {  // in place: exclusive; [nblocks] = grand total
   __shared__ unsigned int s_w[kBlock / 64];
   unsigned int carry = 0;
@@ -3377,7 +3377,7 @@ k_piece_block_scan(unsigned int* __restrict__ block_sum, int nblocks) {  // in p
   }
   if (threadIdx.x == 0) block_sum[nblocks] = carry;
 }
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_piece_offsets(gm_csr_t S, const int32_t* __restrict__ list, int nlist, const unsigned int* __restrict__ block_base,
                 unsigned int* __restrict__ off) {
   __shared__ unsigned int s_w[kBlock / 64];
@@ -3418,7 +3418,7 @@ k_send_list(ProgArg<P> pa, const V* __restrict__ vp, const int32_t* __restrict__
 
 // bids: one workgroup per 1024-edge piece of an active source's out-edges.  The first bid
 // a destination receives also puts it on the `touched` list (its slot of `best` was 0 before).
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_push_bid(gm_csr_t S /* rows = sources */, const int32_t* __restrict__ list, int nlist,
            const unsigned int* __restrict__ off, const int32_t* __restrict__ native_of_dev,
            unsigned long long* __restrict__ best,
@@ -3458,7 +3458,7 @@ k_push_bid(gm_csr_t S /* rows = sources */, const int32_t* __restrict__ list, in
 // out-edges, each vertex only a handful (the late levels of a traversal: a million vertices of degree ~1): the
 // active BITMAP is scanned, one lane per vertex, and every active lane walks its own short out-edge list -- no
 // list, no piece offsets.  (A bottom-up level would scan every unvisited row for these few messages.)
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_push_bid_bits(gm_csr_t S /* rows = sources */, const uint32_t* __restrict__ active, int n,
                 const int32_t* __restrict__ native_of_dev, unsigned long long* __restrict__ best,
                 const uint32_t* __restrict__ want, int32_t* __restrict__ touched, unsigned int* __restrict__ tcount) {
@@ -3673,7 +3673,7 @@ k_push_resolve(ProgArg<P> pa, gm_csr_t S, const T* __restrict__ x, const int32_t
 // While the active set is small the bottom-up kernels test this 128 KB table first: most of their
 // presence tests then never touch the 8 MB vector (level 1 of BFS RMAT-26: half of the short-row
 // kernel's time was those gathers).
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_bits_summary(const uint32_t* __restrict__ bits, int nwords, uint32_t* __restrict__ sum, int nsum) {
   const int t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= nsum) return;
@@ -3733,7 +3733,7 @@ k_unpack_frontier(const sparse_entry<T>* __restrict__ all, int64_t n, T* __restr
 // mark[v] := 1 for every destination v of an out-edge of an active vertex (S: rows = sources).  One lane per vertex of the active bitmap; a
 // vertex of more than 32 out-edges is walked by its whole wave.  The pull multiply of an ORDERED program then folds only the marked rows --
 // every other row has no present message -- and folds them exactly as before.
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_mark_rows_of_active(gm_csr_t S, const uint32_t* __restrict__ active, int n, uint32_t* __restrict__ mark) {
   const int lane = threadIdx.x & 63;
   for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += (int64_t)gridDim.x * kBlock) {
@@ -3755,7 +3755,7 @@ k_mark_rows_of_active(gm_csr_t S, const uint32_t* __restrict__ active, int n, ui
 }
 // the same from the LIST of the active vertices (while they are few): one workgroup per 1024-edge piece of a listed vertex's out-edges
 // (k_piece_offsets), so that a hub's 10^6 out-edges are spread over the chip instead of being walked by one wave (6 ms for RMAT-26's)
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_mark_rows_of_list(gm_csr_t S, const int32_t* __restrict__ list, int nlist, const unsigned int* __restrict__ off, uint32_t* __restrict__ mark) {
   int u;
   int64_t e0, e1;
@@ -3770,7 +3770,7 @@ k_mark_rows_of_list(gm_csr_t S, const int32_t* __restrict__ list, int nlist, con
 // ---- the sharded swept schedule (engine.hpp: run_swept_sharded; round 6) ---------------------------------------------------------------
 // nog = bits & ~(bits of the listed rows), only = bits of the listed rows: the rows every shard applies while its giant rows' fold
 // passes are still running, and the giant rows themselves (both arrays initialised by the caller: nog = a copy of bits, only = 0)
-__global__ void __launch_bounds__(kBlock)
+inline __global__ void __launch_bounds__(kBlock)
 k_split_row_bits(const int32_t* __restrict__ list, int nlist, uint32_t* __restrict__ nog, uint32_t* __restrict__ only) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= nlist) return;
@@ -3812,7 +3812,7 @@ k_apply_send_list(ProgArg<P> pa, const U* __restrict__ y, const uint32_t* __rest
 }
 
 // ------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_fill_u32(uint32_t* __restrict__ p, int64_t n, uint32_t v) {
+inline __global__ void __launch_bounds__(kBlock) k_fill_u32(uint32_t* __restrict__ p, int64_t n, uint32_t v) {
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i < n) p[i] = v;
 }

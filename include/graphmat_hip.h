@@ -578,13 +578,36 @@ int gm_run_rmse(gm_graph_t* g, void* d_latent, int K, int real_bytes, gm_stream_
 int gm_run_sgd_bipartite(gm_graph_t* g, void* d_latent, int K, int real_bytes, const int32_t* d_item_rows, int nitems, int blocks,
                          double lambda, double step, int iterations, int* iters_done, gm_stream_t stream);
 
+/* LDA topic modelling (src/LDA.cpp of the reference): a corpus as a bipartite graph, documents = vertices 1..ndoc, words the
+ * next nterms, an edge document -> word carries a token count (4-byte int).  Vertex state is the reference's
+ * LatentVector<20>: 20 topic counts, type 'd' (document) or 'w' (word), and the word's log-likelihood term.  K = 20, fp64,
+ * whole (unsharded) graphs with both directions and 4-byte values; anything else is GM_ERR_UNSUPPORTED.  d_vp covers the
+ * graph's rows in device order.  Default: dedicated kernels (a wave per row); option "force_ordered" = 1 runs the same
+ * programs through the common engine instead -- the results are bit-identical.
+ *   gm_run_lda_init    N = sum over the vertex's edges (both directions) of the edge's init product; vertices without
+ *                      edges keep their state
+ *   gm_lda_global_n    h_out[k] = sum of N[k] over the word vertices, in a fixed order: the same bits on every call
+ *   gm_run_lda         `iterations` (>= 1) steps with global_N recomputed before the first and after every step;
+ *                      h_global_N (may be NULL) receives the sums of the final state
+ *   gm_run_lda_loglik  token_loglik of every word = sum over its edges of count * log(phi . theta); *h_total = their sum
+ *   gm_lda_edge_init   host only: the init product of one edge (20 shares of edge_value drawn with glibc's rand_r seeded
+ *                      with edge_value), by the function the kernels call */
+typedef struct { double N[20]; char type; double token_loglik; } gm_lda20_t; /* 176 bytes */
+int gm_run_lda_init(gm_graph_t* g, gm_lda20_t* d_vp, int K, gm_stream_t stream);
+int gm_lda_global_n(gm_graph_t* g, const gm_lda20_t* d_vp, int K, double* h_out, gm_stream_t stream);
+int gm_run_lda(gm_graph_t* g, gm_lda20_t* d_vp, int K, double alpha, double eta, double vocab_size, int iterations, int* iters_done,
+               double* h_global_N, gm_stream_t stream);
+int gm_run_lda_loglik(gm_graph_t* g, gm_lda20_t* d_vp, int K, double eta, int nterms, double* h_total, gm_stream_t stream);
+int gm_lda_edge_init(int edge_value, int K, double* h_out);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
  * of more than this many edges get a wave each instead of sharing one 16 to a wave; 0 = GM_LONG_MID rule), "tile_balance"
  * (1: column tiles serve equally many gathers, the default; 0: they hold equally many vertices with edges); "sgd_mfma"
  * (0/1: the dot products of K = 128 fp32 SGD on the matrix cores: an opt-in measurement form whose results deviate from the vector
- * form's -- the reference's -- bits by up to ~1e-5 of the vectors' scale, outside the 1e-6 bar; slower as well).
+ * form's -- the reference's -- bits by up to ~1e-5 of the vectors' scale, outside the 1e-6 bar; slower as well);
+ * "lda_tile" (16 / 32 / 64: edges per step of the dedicated LDA multiply kernel, a measurement knob; results do not depend on it).
  * Every field of gm_engine_options_t below is also a key: gm_set_option then sets the PROCESS default, which a graph
  * uses unless gm_graph_set_option gave it a value of its own; the environment variable GRAPHMAT_OPTIONS="key=value,..."
  * sets such defaults for applications that cannot call this themselves (the reference's unchanged sources). */
