@@ -980,6 +980,7 @@ class Run {
     GM_HIP_OK(hipStreamSynchronize(s));
     gm_graph_note_set(g, 3, (int64_t)sparse_sweeps);
     gm_graph_note_set(g, 4, (int64_t)short_folds);
+    gm_graph_note_set(g, 7, (int64_t)fold_applies);
     gm_graph_note_set(g, 5, (int64_t)((unsigned long long)step_count[STEP_PULL] | (unsigned long long)step_count[STEP_LIST] << 16 |
                                       (unsigned long long)step_count[STEP_BITS] << 32 | (unsigned long long)step_count[STEP_DENSE_PUSH] << 48));
     gm_graph_note_set(g, 6, (int64_t)step_kinds);
@@ -1301,6 +1302,22 @@ class Run {
     }
   }
 
+  // The rows that still need an apply pass behind a multiply whose fold applied the short rows: presence bits of the rows with in-edges
+  // that are not short (the sweep's and the giant rows).  Made once per graph into workspace slot 18, which nothing else uses: the slot
+  // exists exactly when the mask has been written (a graph's sweep structure and presence bits never change).
+  const uint32_t* fold_rest_mask(const gm_sweep_t& sw) {
+    const size_t need = ((size_t)nwords + 2) * 4;
+    void* pm = nullptr;
+    size_t have = 0;
+    int ext = 0;
+    if (gm_graph_workspace_info(g, 18, &pm, &have, &ext) == GM_OK && pm != nullptr && have >= need) return (const uint32_t*)pm;
+    if (sw.srow == nullptr || sw.nshort_rows <= 0 || Aout.rowbits == nullptr || gm_graph_workspace(g, 18, need, &pm) != GM_OK || pm == nullptr) return nullptr;
+    GM_HIP_OK(hipMemsetAsync(pm, 0, need, s));
+    GM_HIP_OK(hipMemcpyAsync(pm, Aout.rowbits, (size_t)nwords * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(dev::k_clear_row_bits, dim3(grid_for(sw.nshort_rows)), dim3(dev::kBlock), 0, s, sw.srow, (int)sw.nshort_rows, (uint32_t*)pm);
+    return (const uint32_t*)pm;
+  }
+
   // The OUT adjacency through the sweep: the giant rows' passes (products spread over the chip, then the exact replay or the
   // ordered fold: a chain of small latency-bound launches) on the auxiliary stream from the moment x is complete, the short
   // rows (row-blocks of the whole-graph CSR) and the sweep's launches on the main stream; joined before apply.  sweep_form:
@@ -1491,8 +1508,27 @@ class Run {
       }
       if (where == 2) short_rows();
       if (where == 4) {  // the short rows' fold from the products the sweep left (next to the giant rows' fold passes on the auxiliary stream)
-        hipLaunchKernelGGL((dev::k_short_fold<P, U>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap, sw.sbin_row,
-                           sw.soff, sw.srow, y, (acc & dev::ACC_STATIC_BITS) ? (uint32_t*)nullptr : ybits);
+        // Fold + apply + send (sweep_form bit 9 refuses it).  The fold writes x in place, so nothing of this multiply may read x beside or behind
+        // it: one shard, all sweep launches in front of it on this stream, the giant rows' products gathered by the sweep (their passes on the
+        // auxiliary stream then read the products stream only: k_giant_sums / k_giant_maps / k_giant_replay_maps, launch_spmv's two-pass float
+        // form WITH piece maps -- without maps k_spmv_giant gets x), no column-blocked tail, no cross-check of a probed strategy (it folds sampled
+        // rows again from x).  The rows that are neither short nor without in-edges are applied by step_pull behind the join (fold_rest_mask).
+        bool fused_fold = false;
+        if constexpr (std::is_trivially_copyable<V>::value && sizeof(V) <= 16) {
+          const bool giants_off_x = Aout.ngiant == 0 || (gterms != nullptr && !gather_apart && opt.giant_maps != 0 && Aout.gchunk_state != nullptr);
+          if (fold_apply_want && !(opt.sweep_form & 512) && sw.nsub <= 1 && !multi && !defer_join && (acc & dev::ACC_STATIC_BITS) && giants_off_x && !shorts_blocked &&
+              !rk_unverified && d_want == nullptr && xq == (const T*)x && fold_rest_mask(sw) != nullptr) {
+            hipLaunchKernelGGL((dev::k_short_fold<P, U, T, V, true>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap,
+                               sw.sbin_row, sw.soff, sw.srow, y, (uint32_t*)nullptr, d_vp, x, desc.row_lo);
+            fused_fold = true;
+            fold_applied = true;
+            fold_applies++;
+            if (verbose && !said_fold_apply) { printf("GraphMat(HIP):   the fold applies its rows and sends their next messages (k_short_fold, fused; no pass over y for them)\n"); said_fold_apply = true; }
+          }
+        }
+        if (!fused_fold)
+          hipLaunchKernelGGL((dev::k_short_fold<P, U>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap, sw.sbin_row,
+                             sw.soff, sw.srow, y, (acc & dev::ACC_STATIC_BITS) ? (uint32_t*)nullptr : ybits);
         st.spmv_launches++;
         short_folds++;
         if (verbose && !said_short_fold) { printf("GraphMat(HIP):   the rows of up to %d edges ride the sweep (k_short_fold)\n", (int)sw.short_row); said_short_fold = true; }
@@ -1637,6 +1673,10 @@ class Run {
   bool said_blocked = false, said_sparse_sweep = false, said_short_fold = false;
   int sparse_sweeps = 0;  // multiplies of this run that took a sparse x through the sweep (note 3 of the graph: tests read it)
   int short_folds = 0;    // multiplies of this run whose short rows were folded from the sweep's products stream (note 4)
+  // fold + apply + send (kernels.hpp: k_short_fold, FUSED): step_pull says before a multiply that today's path would run k_apply_send behind it
+  // (fold_apply_want); multiply_out_swept answers whether its fold applied the short rows and sent for them (fold_applied)
+  bool fold_apply_want = false, fold_applied = false, said_fold_apply = false;
+  int fold_applies = 0;   // multiplies of this run whose fold also applied and sent (note 7)
   // which step every iteration of run_loop took (graphmat_hip.h: notes 5 and 6 of the graph: tests compare them with the rule restated on the host)
   enum { STEP_PULL = 0, STEP_LIST = 1, STEP_BITS = 2, STEP_DENSE_PUSH = 3 };
   unsigned int step_count[4] = {0, 0, 0, 0};  // iterations per kind, saturating at 65535
@@ -1841,6 +1881,10 @@ class Run {
       guided_few = frontier_e <= 4096ull;
       if (verbose) printf("GraphMat(HIP):   guided pull: %llu active vertices, %llu out-edges\n", frontier_v, frontier_e);
     }
+    // would k_apply_send run behind this multiply (the test below)?  Then the short rows' fold may apply and send (multiply_out_swept)
+    fold_applied = false;
+    fold_apply_want = !want_stats && inherits_iteration_hook<P>() && dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations &&
+                      order == OUT_EDGES && !dense_push && !xsp;
     if (dense_push) {
       multiply_dense_push(pa);
     } else if (order == OUT_EDGES || order == ALL_EDGES) {
@@ -1901,7 +1945,16 @@ class Run {
     if (want_stats)
       hipLaunchKernelGGL((dev::k_apply<P, U, V, true>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, apply_bits, d_vp, d_active, n_live,
                          d_changed, Asrc.rowptr, d_striped, d_want, build_list ? d_list : (int32_t*)nullptr, build_list ? d_count : (unsigned int*)nullptr);
-    else if (inherits_iteration_hook<P>() && dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations) {
+    else if (fold_applied) {
+      // the fold applied the short rows and wrote their next messages: what remains are the sweep's and the giant rows (fold_rest_mask); rows
+      // without in-edges keep their property and the message of the run's first send.  The active vector, the changed flag and x's presence
+      // words are not touched: a fixed-count run reads none of them before its last iteration, whose plain k_apply rewrites the first two for
+      // every row (the presence words are all set since the first send)
+      gm_sweep_t swm;
+      gm_graph_sweep(g, &swm);
+      hipLaunchKernelGGL((dev::k_apply_send_masked<P, T, U, V>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, fold_rest_mask(swm), d_vp, n_live, x, desc.row_lo);
+      x_presend = true;
+    } else if (inherits_iteration_hook<P>() && dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations) {
       // another iteration follows: its messages come out of the same pass.  Only for programs without a do_every_iteration
       // of their own (nothing can change what send_message reads between the two iterations), and only in fixed-count
       // runs: until convergence the last iteration is not known in advance, and a fused pass there would leave x holding
@@ -1914,6 +1967,7 @@ class Run {
                          d_changed, (const int64_t*)nullptr, (unsigned long long*)nullptr, d_want, (int32_t*)nullptr, (unsigned int*)nullptr);
     if (n_live < n && it == 0)  // setAllInactive for the rows k_apply does not visit (they have no edges: once clear, nothing sets them again)
       GM_HIP_OK(hipMemsetAsync(d_active + n_live / 32, 0, (size_t)(nwords - n_live / 32) * 4, s));
+    fold_apply_want = false;
     timer.mark(TAG_APPLY);
     lap("Apply time");
   }

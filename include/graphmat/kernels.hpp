@@ -1904,11 +1904,17 @@ k_spmv_sell_stream(ProgArg<P> pa, int set, int stage_words, int nslices, int nro
 // bin's CSR order, the products are put there in LDS -- all chunks' entries dealt flat over the threads -- and one thread per row folds its run
 // in ascending native column order: the first message assigns (spmspv.h:73-77), like every other kernel of the path.  ybits = nullptr: the
 // presence bits are the graph's static ones.
-template <class P, class U>
+// A thread's rows are 512 apart (round j: row i0 + 512 j + thread).  What a round needs from global memory -- soff[i], soff[i + 1], srow_id[i] --
+// is requested three rounds ahead into one of four register sets (the loop is unrolled four times, so a set is named statically and nothing is
+// moved between them): a bin of 1-edge rows has 24 rounds, and none but the first waits for its row's offsets.
+// FUSED (engine.hpp: fold + apply + send): the row just folded is applied and sends the NEXT iteration's message -- exactly k_apply_send's
+// arithmetic: apply on a private copy of the program, send_message with the program as captured -- so nothing is written to y and no pass
+// over the vertices reads it back.  vp[row] of the next round is requested one round ahead (its row id arrived two rounds before that).
+template <class P, class U, class T = U, class V = int, bool FUSED = false>
 __global__ void __launch_bounds__(512, 6)
 k_short_fold(ProgArg<P> pa, const U* __restrict__ sterms, const uint16_t* __restrict__ sinv, const uint32_t* __restrict__ schunk, int nslices, int cap,
              const uint32_t* __restrict__ sbin_row, const uint32_t* __restrict__ soff, const int32_t* __restrict__ srow_id, U* __restrict__ y,
-             uint32_t* __restrict__ ybits) {
+             uint32_t* __restrict__ ybits, V* __restrict__ vp = nullptr, T* __restrict__ x = nullptr, int row_base = 0) {
   static_assert(sizeof(U) == 4, "4-byte reductions");
   // (a bin's rows are degree-ranked: neighbouring threads fold rows of the SAME length L, i.e. read LDS L words apart -- one pad word per 32 keeps
   // L = 16 / 32 / 64 off a single bank)
@@ -1919,14 +1925,18 @@ k_short_fold(ProgArg<P> pa, const U* __restrict__ sterms, const uint16_t* __rest
   const int b = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t* __restrict__ raw = reinterpret_cast<const uint32_t*>(sterms);
   const uint32_t i0 = sbin_row[b], i1 = sbin_row[b + 1], base = (uint32_t)b * (uint32_t)cap;
-  // this thread's first rows are requested while the products arrive
-  constexpr int RK = 4;
+  if (i0 >= i1) return;  // (a bin without rows has no products either; the whole workgroup leaves)
+  // this thread's first rows are requested while the products arrive.  Every request is UNCONDITIONAL -- a round past the bin's end asks for
+  // the bin's last row again and its answer is not used: a load under a condition costs a branch, and where its two sides meet the compiler
+  // waits for everything in flight
+  const uint32_t ilast = i1 - 1u;
+  constexpr int RK = 4;  // register sets: rounds j .. j + 3
   uint32_t ro0[RK], ro1[RK];
   int rid[RK];
 #pragma unroll
-  for (int j = 0; j < RK; j++) {
-    const uint32_t i = i0 + (uint32_t)(j * 512) + threadIdx.x;
-    if (i < i1) { ro0[j] = soff[i]; ro1[j] = soff[i + 1]; rid[j] = srow_id[i]; }
+  for (int j = 0; j < RK - 1; j++) {
+    const uint32_t iq = i0 + (uint32_t)(j * 512) + threadIdx.x, i = iq < ilast ? iq : ilast;
+    ro0[j] = soff[i]; ro1[j] = soff[i + 1]; rid[j] = srow_id[i];
   }
   if ((int)threadIdx.x < nslices) {  // where the bin's products of every slice are, and how many
     const uint2 pn = *reinterpret_cast<const uint2*>(&schunk[((size_t)b * nslices + threadIdx.x) * 2]);
@@ -1965,37 +1975,87 @@ k_short_fold(ProgArg<P> pa, const U* __restrict__ sterms, const uint16_t* __rest
       for (uint32_t i = (uint32_t)(CK * 64 + lane); i < cn[c]; i += 64u) s_prod[at(sinv[cp[c] + i])] = raw[cp[c] + i];  // (a chunk of more than 256 products)
     }
   }
+  V cv[2];  // FUSED: the vertex properties of this round's and the next round's row
+  if constexpr (FUSED) cv[0] = vp[rid[0]];  // (in flight across the barrier)
   __syncthreads();
   auto as_u = [](uint32_t r) { U u; __builtin_memcpy(&u, &r, 4); return u; };
-  for (uint32_t ii = i0 + (uint32_t)(wv * 64), jj = 0; ii < i1; ii += 512u, jj++) {
-    const uint32_t i = ii + (uint32_t)lane;
-    const bool valid = i < i1;
-    int row = 0;
-    if (valid) {
-      uint32_t o0, o1;
-      if (jj < RK) {
-        o0 = ro0[0]; o1 = ro1[0]; row = rid[0];
+  for (uint32_t ii = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i0 + (uint32_t)(wv * 64))); ii < i1;) {
 #pragma unroll
-        for (int j = 1; j < RK; j++) if ((int)jj == j) { o0 = ro0[j]; o1 = ro1[j]; row = rid[j]; }
-      } else { o0 = soff[i]; o1 = soff[i + 1]; row = srow_id[i]; }
-      o0 -= base; o1 -= base;
-      U acc = as_u(s_prod[at(o0)]);
-      for (uint32_t k = o0 + 1; k < o1; k++) p.P::reduce_function(acc, as_u(s_prod[at(k)]));
-      y[row] = acc;
-    }
-    if (ybits != nullptr) {  // (rows of a run are consecutive device ids: three words per wave instead of 64 atomics)
-      const int r0 = __builtin_amdgcn_readfirstlane(row);
-      if (__all(!valid || row == r0 + lane)) {
-        const unsigned long long hb = __ballot(valid);
-        const int sh = r0 & 31;
-        const unsigned long long lo = hb << sh, hi = sh ? (hb >> (64 - sh)) : 0ull;
-        const uint32_t w = lane == 0 ? (uint32_t)lo : lane == 1 ? (uint32_t)(lo >> 32) : lane == 2 ? (uint32_t)hi : 0u;
-        if (lane < 3 && w != 0u) atomicOr(&ybits[(r0 >> 5) + lane], w);
-      } else if (valid) {
-        atomicOr(&ybits[row >> 5], 1u << (row & 31));
+    for (int u = 0; u < RK; u++, ii += 512u) {
+      if (ii >= i1) break;  // (wave-uniform)
+      const uint32_t i = ii + (uint32_t)lane;
+      const bool valid = i < i1;
+      if constexpr (FUSED) cv[(u + 1) & 1] = vp[rid[(u + 1) & (RK - 1)]];  // (the next round's row id arrived two rounds ago)
+      {
+        const uint32_t iq = i + (uint32_t)((RK - 1) * 512), ia = iq < ilast ? iq : ilast;
+        const int ua = (u + RK - 1) & (RK - 1);  // (the set the previous round has just used)
+        ro0[ua] = soff[ia]; ro1[ua] = soff[ia + 1]; rid[ua] = srow_id[ia];
+      }
+      const int row = rid[u];
+      if (valid) {
+        const uint32_t o0 = ro0[u] - base, o1 = ro1[u] - base;
+        U acc = as_u(s_prod[at(o0)]);
+        for (uint32_t k = o0 + 1; k < o1; k++) p.P::reduce_function(acc, as_u(s_prod[at(k)]));
+        if constexpr (FUSED) {
+          ProgArg<P> local = pa;  // apply() is non-const in the API: give it a private copy
+          P& pl = *reinterpret_cast<P*>(local.b);
+          V cur = cv[u & 1];
+          pl.P::apply(acc, cur);
+          vp[row] = cur;
+          T m;
+          p.P::send_message(cur, m);  // (the send of the NEXT iteration: the program as captured, not apply's copy)
+          x[(size_t)row_base + row] = m;
+        } else {
+          y[row] = acc;
+        }
+      }
+      if constexpr (!FUSED) {
+        if (ybits != nullptr) {  // (rows of a run are consecutive device ids: three words per wave instead of 64 atomics)
+          const int r0 = __builtin_amdgcn_readfirstlane(row);
+          if (__all(!valid || row == r0 + lane)) {
+            const unsigned long long hb = __ballot(valid);
+            const int sh = r0 & 31;
+            const unsigned long long lo = hb << sh, hi = sh ? (hb >> (64 - sh)) : 0ull;
+            const uint32_t w = lane == 0 ? (uint32_t)lo : lane == 1 ? (uint32_t)(lo >> 32) : lane == 2 ? (uint32_t)hi : 0u;
+            if (lane < 3 && w != 0u) atomicOr(&ybits[(r0 >> 5) + lane], w);
+          } else if (valid) {
+            atomicOr(&ybits[row >> 5], 1u << (row & 31));
+          }
+        }
       }
     }
   }
+}
+// The rest of the rows behind a multiply whose short rows were applied by the fold (k_short_fold, FUSED): apply + the next iteration's
+// send where `mask` has a bit -- the rows with in-edges that are NOT short (the sweep's and the giant rows).  A row without a bit is not
+// visited: a short row is done, and a live row without in-edges keeps its property and the message the run's first send wrote.  Same
+// arithmetic as k_apply_send; the active vector, the changed flag and x's presence words are left to the run's last, plain iteration
+// (a fixed-count run reads none of them in between; every live row's presence bit of x is set by the first send and stays).
+template <class P, class T, class U, class V>
+__global__ void __launch_bounds__(kBlock)
+k_apply_send_masked(ProgArg<P> pa, const U* __restrict__ y, const uint32_t* __restrict__ mask, V* __restrict__ vp, int n, T* __restrict__ x, int row_base) {
+  for (int64_t base = (int64_t)blockIdx.x * kBlock; base < n; base += (int64_t)gridDim.x * kBlock) {
+    const int i = (int)base + threadIdx.x;
+    if (i < n && bit_get(mask, i)) {
+      ProgArg<P> local = pa;
+      P& p = *reinterpret_cast<P*>(local.b);
+      V cur = vp[i];
+      p.P::apply(y[i], cur);
+      vp[i] = cur;
+      const P& ps = *reinterpret_cast<const P*>(pa.b);
+      T m;
+      ps.P::send_message(cur, m);
+      x[(size_t)row_base + i] = m;
+    }
+  }
+}
+// mask &= ~(bits of the listed rows)
+inline __global__ void __launch_bounds__(kBlock)
+k_clear_row_bits(const int32_t* __restrict__ list, int nlist, uint32_t* __restrict__ mask) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nlist) return;
+  const int r = list[i];
+  atomicAnd(&mask[r >> 5], ~(1u << (r & 31)));
 }
 // The giant rows' gathers in a kernel of their own (engine option sweep_form bit 4): gm_sweep_t.gcol is sorted by slice, so a grid-stride
 // walk keeps all workgroups inside about one slice of the message vector at a time (L2-resident) without hot sets.  Runs on the auxiliary

@@ -527,7 +527,10 @@ int gm_graph_split(const gm_graph_t* g, int direction, int head_permille, int32_
  *   5: iterations per kind, 16 bits each, saturating: pull | list << 16 | bits << 32 | dense_push << 48
  *   6: the kinds of the first 32 iterations, two bits each: iteration i in bits 2i..2i+1
  * A run that does not go through that loop (the fixed-count two-stage and sharded swept schedules)
- * leaves both at 0. */
+ * leaves both at 0.
+ * Slots 3, 4 and 7 are written at the end of every run too: the multiplies of the run that took a sparse
+ * message vector through the sweep (3), whose short rows were folded from the sweep's products stream (4),
+ * and whose fold also applied its rows and sent their next messages (7: k_short_fold's fused form). */
 #define GM_NOTE_SLOTS 8
 int gm_graph_note_set(gm_graph_t* g, int slot, int64_t value);
 int gm_graph_note_get(const gm_graph_t* g, int slot, int64_t* value);
@@ -657,7 +660,7 @@ typedef struct {
                                      2 on the main stream behind the sweep; bit 2 = the long rows staged in rounds of 1024 entries (tests); bit 3 = the
                                      giant rows gather for themselves on the auxiliary stream (k_giant_terms) instead of the sweep gathering for them; bit 4 = the giant rows' gathers in a
                                      kernel of their own behind the sweep (k_giant_gather_sliced: their entries in slice order, on the auxiliary stream next to the short rows); bit 5 = a SPARSE
-                                     message vector (ACTIVE_ONLY programs) does not take the sweep (k_spmv_sell_sparse); bit 6 = it does on graphs of any size (default: from 2e8 edges on); bit 7 = the short rows keep the row-block kernel (gm_sweep_t.nstream is not used); bit 8 = they ride the sweep whatever their number (default: from 2^25 short-row edges on) */
+                                     message vector (ACTIVE_ONLY programs) does not take the sweep (k_spmv_sell_sparse); bit 6 = it does on graphs of any size (default: from 2e8 edges on); bit 7 = the short rows keep the row-block kernel (gm_sweep_t.nstream is not used); bit 8 = they ride the sweep whatever their number (default: from 2^25 short-row edges on); bit 9 = their fold never applies and sends (k_short_fold's fused form; default: it does in the iterations of a fixed-count run that k_apply_send would follow) */
   int32_t blocked_form;           /* the column-blocked stream of the short rows (engine.hpp: multiply_out_blocked): bits 0-3 = window -- a workgroup starts a
                                      slice when all workgroups of its XCD have finished the one `window` slices back (default 2; 0 = workgroups not
                                      kept in step); bit 4 = batches of 4 x 64 entries instead of 2 x 64 */
