@@ -668,6 +668,13 @@ int run_rmse_wide(gm_graph_t* g, float* d_latent, hipStream_t s) {
   GM_TRY_HIP(hipStreamSynchronize(s));
   return GM_OK;
 }
+// which path a gm_run_sgd / gm_run_rmse / gm_run_sgd_bipartite call takes (graphmat_hip.h: GM_NOTE_SGD_PATH), for tests: a host
+// integer on the graph, nothing a kernel sees
+static void note_sgd_path(gm_graph_t* g, int path) {
+  if (!g) return;
+  g->note_val[GM_NOTE_SGD_PATH] = path;
+  g->note_set[GM_NOTE_SGD_PATH] = 1;
+}
 static bool wide_path_ok(const gm_graph_t* g) {
   const bool whole = g && g->desc.row_lo == 0 && g->desc.row_hi == g->desc.ndevice;
   return g && g->out.present && g->in.present && g->desc.val_bytes == 4 && g->out.vals && g->in.vals &&
@@ -893,6 +900,9 @@ int gm_run_sssp(gm_graph_t* g, uint32_t* d_dist, uint32_t* d_active, int iterati
 int gm_run_sgd(gm_graph_t* g, void* d_latent, int K, int real_bytes, double lambda, double step, int iterations,
                int* iters_done, gm_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
+  const bool wide = K == 128 && real_bytes == 4 && iterations > 0 && gm::wide_path_ok(g) && d_latent;
+  if ((K == 20 && (real_bytes == 8 || real_bytes == 4)) || (K == 128 && real_bytes == 4))
+    gm::note_sgd_path(g, !wide ? GM_SGD_PATH_ENGINE : gm::g_sgd_mfma ? GM_SGD_PATH_MFMA : GM_SGD_PATH_VECTOR);
   if (K == 20 && real_bytes == 8) {
     gm::SgdP<double, 20> p(lambda, step);
     return gm::run_fixed(p, g, (gm::Latent<double, 20>*)d_latent, (uint32_t*)nullptr, iterations, iters_done, s);
@@ -901,7 +911,7 @@ int gm_run_sgd(gm_graph_t* g, void* d_latent, int K, int real_bytes, double lamb
     gm::SgdP<float, 20> p((float)lambda, (float)step);
     return gm::run_fixed(p, g, (gm::Latent<float, 20>*)d_latent, (uint32_t*)nullptr, iterations, iters_done, s);
   }
-  if (K == 128 && real_bytes == 4 && iterations > 0 && gm::wide_path_ok(g) && d_latent)
+  if (wide)
     return gm::run_sgd_wide<128>(g, (float*)d_latent, (float)lambda, (float)step, iterations, iters_done, s);
   if (K == 128 && real_bytes == 4) {
     gm::SgdP<float, 128> p((float)lambda, (float)step);
@@ -921,12 +931,16 @@ int gm_run_sgd_bipartite(gm_graph_t* g, void* d_latent, int K, int real_bytes, c
     gm::set_error("gm_run_sgd_bipartite: needs an unsharded graph of this rank's users' ratings, both directions, 4-byte values");
     return GM_ERR_INVALID;
   }
+  gm::note_sgd_path(g, GM_SGD_PATH_RING);
   return gm::run_sgd_bipartite<128>(g, (float*)d_latent, d_item_rows, nitems, blocks, (float)lambda, (float)step, iterations, iters_done,
                                     (hipStream_t)stream);
 }
 
 int gm_run_rmse(gm_graph_t* g, void* d_latent, int K, int real_bytes, gm_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
+  const bool wide = K == 128 && real_bytes == 4 && gm::wide_path_ok(g) && d_latent;
+  if ((K == 20 && (real_bytes == 8 || real_bytes == 4)) || (K == 128 && real_bytes == 4))
+    gm::note_sgd_path(g, wide ? GM_SGD_PATH_VECTOR : GM_SGD_PATH_ENGINE);
   if (K == 20 && real_bytes == 8) {
     gm::RmseP<double, 20> p;
     return gm::run_fixed(p, g, (gm::Latent<double, 20>*)d_latent, (uint32_t*)nullptr, 1, nullptr, s);
@@ -935,7 +949,7 @@ int gm_run_rmse(gm_graph_t* g, void* d_latent, int K, int real_bytes, gm_stream_
     gm::RmseP<float, 20> p;
     return gm::run_fixed(p, g, (gm::Latent<float, 20>*)d_latent, (uint32_t*)nullptr, 1, nullptr, s);
   }
-  if (K == 128 && real_bytes == 4 && gm::wide_path_ok(g) && d_latent) return gm::run_rmse_wide<128>(g, (float*)d_latent, s);
+  if (wide) return gm::run_rmse_wide<128>(g, (float*)d_latent, s);
   if (K == 128 && real_bytes == 4) {
     gm::RmseP<float, 128> p;
     return gm::run_fixed(p, g, (gm::Latent<float, 128>*)d_latent, (uint32_t*)nullptr, 1, nullptr, s);

@@ -530,8 +530,15 @@ int gm_graph_split(const gm_graph_t* g, int direction, int head_permille, int32_
  * leaves both at 0.
  * Slots 3, 4 and 7 are written at the end of every run too: the multiplies of the run that took a sparse
  * message vector through the sweep (3), whose short rows were folded from the sweep's products stream (4),
- * and whose fold also applied its rows and sent their next messages (7: k_short_fold's fused form). */
-#define GM_NOTE_SLOTS 8
+ * and whose fold also applied its rows and sent their next messages (7: k_short_fold's fused form).
+ * Slot 8 is written by gm_run_sgd, gm_run_rmse and gm_run_sgd_bipartite when they choose their kernels: the path the
+ * call takes, one of GM_SGD_PATH_* (a call refused for its K, real_bytes or graph leaves the slot as it was). */
+#define GM_NOTE_SLOTS 9
+#define GM_NOTE_SGD_PATH 8
+#define GM_SGD_PATH_ENGINE 0 /* the program went through the common engine (run_graph_program's kernels) */
+#define GM_SGD_PATH_VECTOR 1 /* the dedicated K = 128 fp32 kernels, dot products on the vector units (k_sgd_multiply) */
+#define GM_SGD_PATH_MFMA 2   /* the dedicated kernels with option "sgd_mfma": dot products on the matrix cores */
+#define GM_SGD_PATH_RING 3   /* gm_run_sgd_bipartite: the item ring (row-list form of k_sgd_multiply, k_rows_*) */
 int gm_graph_note_set(gm_graph_t* g, int slot, int64_t value);
 int gm_graph_note_get(const gm_graph_t* g, int slot, int64_t* value);
 /* what a workspace slot currently holds (external = adopted from the caller) */

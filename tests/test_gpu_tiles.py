@@ -154,7 +154,8 @@ def test_tile_threshold_must_be_zero_or_at_least_the_short_row_limit(env):
 
 
 def test_other_programs_on_a_tiled_graph(env, tile_min):
-    """BFS / SSSP / SGD do not use the tiles but run on the tiled device order."""
+    """BFS / SSSP do not use the tiles but run on the tiled device order (SGD on a tiled device order:
+    tests/test_gpu_sgd.py::test_ladder_on_a_tiled_device_order)."""
     api, ob = env
     tile_min(64)
     nv, s, d, v = gen.rmat_edges(13, 16, seed=77, weights="hash")
