@@ -47,16 +47,17 @@ class Fold : public GraphMat::GraphProgram<float, float, float> {
 typedef std::vector<GraphMat::edge_t<int> > edges_t;
 
 // how many giant rows the last multiply had to fold again (white box: the engine keeps the chunk boundaries and the per-row flags of
-// k_giant_verify_chunks in workspace slot 15 of the graph: [ngchunk + 2] boundaries of 8 bytes, then one int per giant row); -1 = no speculation ran
+// k_giant_verify_chunks in workspace slot GM_WS_SPECULATION of the graph, laid out by engine.hpp's spec_layout); -1 = no speculation ran
 static int rows_folded_again(GraphMat::Graph<float>& G) {
   gm_csr_t ca;
   if (gm_graph_csr(G.A, GM_DIR_OUT, &ca) != 0) return -1;
   void* ws = nullptr;
   size_t bytes = 0;
   int external = 0;
-  if (gm_graph_workspace_info(G.A, 15, &ws, &bytes, &external) != 0 || ws == nullptr || bytes < ((size_t)ca.ngchunk + 2) * 8 + (size_t)ca.ngiant * 4) return -1;
+  const GraphMat::detail::SpecLayout lay = GraphMat::detail::spec_layout(ca.ngchunk, ca.ngiant);
+  if (gm_graph_workspace_info(G.A, GM_WS_SPECULATION, &ws, &bytes, &external) != 0 || ws == nullptr || bytes < lay.redo + (size_t)ca.ngiant * 4) return -1;
   std::vector<int> redo(ca.ngiant);
-  if (hipMemcpy(redo.data(), (const char*)ws + ((size_t)ca.ngchunk + 2) * 8, (size_t)ca.ngiant * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(redo.data(), (const char*)ws + lay.redo, (size_t)ca.ngiant * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   int k = 0;
   for (int r : redo) k += r != 0;
   return k;

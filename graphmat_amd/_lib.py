@@ -15,7 +15,13 @@ GM_XCHG_WAIT = 3
 GM_XCHG_STATE = 4
 GM_XCHG_GATHER = 5
 GM_XCAP_SPARSE = 1
-GM_WS_GATHER = 12
+# workspace and note slots (graphmat_hip.h: the table next to GM_WS_SLOTS, the comment above GM_NOTE_SLOTS)
+GM_WS_FLAGS, GM_WS_X, GM_WS_XBITS, GM_WS_Y, GM_WS_YBITS, GM_WS_ALL_ACTIVE = 0, 1, 2, 3, 4, 5
+GM_WS_GIANT_TERMS = GM_WS_PUSH_BIDS = GM_WS_SGD_ITEM_SUMS = 6
+GM_WS_ACTIVE_LIST, GM_WS_ROW_MARKS, GM_WS_X2, GM_WS_TOUCHED, GM_WS_XSUM, GM_WS_GATHER = 7, 8, 9, 10, 11, 12
+GM_WS_VPROP_STAGE, GM_WS_GIANT_TPRES, GM_WS_SPECULATION, GM_WS_SHORT_TERMS, GM_WS_LDA_SUMS, GM_WS_FOLD_REST_MASK = 13, 14, 15, 16, 17, 18
+GM_NOTE_TWO_STAGE_SPLIT, GM_NOTE_SGD_RING_BYTES, GM_NOTE_GIANT_GATHER_CAP, GM_NOTE_SPARSE_SWEEPS, GM_NOTE_SHORT_FOLDS = 0, 1, 2, 3, 4
+GM_NOTE_STEP_COUNTS, GM_NOTE_STEP_KINDS, GM_NOTE_FOLD_APPLIES, GM_NOTE_SGD_PATH = 5, 6, 7, 8
 GM_LAYOUT_NATIVE = 0
 GM_LAYOUT_DEGREE = 1
 

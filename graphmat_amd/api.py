@@ -258,7 +258,7 @@ class Graph:
         check(self.L.gm_run_sgd_bipartite(self.h, st.data_ptr(), K, st.element_size(), item_rows.data_ptr(), nitems, blocks, lam, step,
                                           iterations, C.byref(it), _stream()))
         moved = C.c_int64(0)
-        self.L.gm_graph_note_get(self.h, 1, C.byref(moved))
+        self.L.gm_graph_note_get(self.h, _lib.GM_NOTE_SGD_RING_BYTES, C.byref(moved))
         return self.to_vertex_order(st)[:, :K].cpu().numpy(), it.value, moved.value
 
     def rmse_sum(self, lv):

@@ -2429,7 +2429,7 @@ int gm_graph_create(gm_graph_t** gout, const gm_graph_desc_t* desc, int64_t nnz,
   void* unused[4];
   if ((rc = gm_graph_run_resources(g, &unused[0], &unused[1], &unused[2], &unused[3])) != GM_OK) { gm_graph_destroy(g); return rc; }
   void* flag = nullptr;
-  if (gm_graph_workspace(g, 0, 4096, &flag) == GM_OK) gm::warm_program_kernels(flag);
+  if (gm_graph_workspace(g, GM_WS_FLAGS, 4096, &flag) == GM_OK) gm::warm_program_kernels(flag);
   *gout = g;
   return GM_OK;
 }

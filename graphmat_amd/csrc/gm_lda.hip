@@ -114,13 +114,13 @@ k_lda_sum(const double* __restrict__ src, int64_t n, int64_t chunk, double* __re
     out[(int64_t)blockIdx.x * kLdaK + k] = t;
   }
 }
-// enqueue both levels; *d_gn (device, K doubles, in workspace slot 17) holds the sums when the stream gets there
+// enqueue both levels; *d_gn (device, K doubles, in workspace slot GM_WS_LDA_SUMS) holds the sums when the stream gets there
 static int lda_global_n(gm_graph_t* g, const gm_lda20_t* d_vp, double** d_gn, hipStream_t s) {
   const int64_t n = g->desc.row_hi - g->desc.row_lo;
   const int64_t nchunks = (n + kLdaSumChunk - 1) / kLdaSumChunk;
   void* p = nullptr;
   int rc;
-  if ((rc = gm_graph_workspace(g, 17, (size_t)(nchunks + 1) * kLdaK * 8 + 64, &p))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_LDA_SUMS, (size_t)(nchunks + 1) * kLdaK * 8 + 64, &p))) return rc;
   double* part = (double*)p;
   *d_gn = part + nchunks * kLdaK;
   hipLaunchKernelGGL((k_lda_sum<true>), dim3((unsigned)nchunks), dim3(kLdaSumBlock), 0, s, (const double*)d_vp, n, (int64_t)kLdaSumChunk, part);
@@ -378,8 +378,8 @@ static int lda_scratch(gm_graph_t* g, LdaScratch* w) {
   w->n = d.row_hi - d.row_lo;
   void *px = nullptr, *py = nullptr;
   int rc;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * kLdaK * 8 + 64, &px))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)w->n * kLdaK * 8 + 64, &py))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_X, (size_t)d.ndevice * kLdaK * 8 + 64, &px))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_Y, (size_t)w->n * kLdaK * 8 + 64, &py))) return rc;
   w->x = (double*)px;
   w->y = (double*)py;
   w->egrid = (int)(((int64_t)w->n * kLdaK + kLdaBlock - 1) / kLdaBlock);

@@ -195,7 +195,7 @@ static int sgd_exchange(gm_graph_t* g, float* x, int K, hipStream_t s) {
   g->run_stream = s;
   void* bits = nullptr;
   int rc;
-  if ((rc = gm_graph_workspace(g, 2, ((size_t)(g->desc.ndevice + 31) / 32 + 2) * 4, &bits))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_XBITS, ((size_t)(g->desc.ndevice + 31) / 32 + 2) * 4, &bits))) return rc;
   if (gm_graph_exchange(g, GM_XCHG_MESSAGES, x, (int64_t)K * 4, (uint32_t*)bits, nullptr) != 0) {
     set_error("gm_run_sgd: message exchange callback failed");
     return GM_ERR_INVALID;
@@ -443,8 +443,8 @@ int run_sgd_wide(gm_graph_t* g, float* d_latent, float lambda, float step, int i
   const int n = d.row_hi - d.row_lo;
   void *px = nullptr, *py = nullptr;
   int rc;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)n * K * 4 + 64, &py))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_X, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_Y, (size_t)n * K * 4 + 64, &py))) return rc;
   const int wgrid = (n + kSgdMulBlock / 64 - 1) / (kSgdMulBlock / 64);
   const int egrid = (int)(((int64_t)n * K + kSgdBlock - 1) / kSgdBlock);
   gm_run_stats_t st;
@@ -542,10 +542,10 @@ int run_sgd_bipartite(gm_graph_t* g, float* d_latent, const int32_t* d_item_rows
   void *px = nullptr, *py = nullptr, *pk = nullptr, *pb = nullptr;
   int rc;
   const size_t nw = (size_t)(n + 31) / 32 + 2;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)n * K * 4 + 64, &py))) return rc;
-  if ((rc = gm_graph_workspace(g, 6, (size_t)nitems * (K + 1) * 4 + 256, &pk))) return rc;  // packed item sums + their flags
-  if ((rc = gm_graph_workspace(g, 4, nw * 4 * 2 + 64, &pb))) return rc;                       // presence bits: received / applied (+ 64 bytes of scratch)
+  if ((rc = gm_graph_workspace(g, GM_WS_X, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_Y, (size_t)n * K * 4 + 64, &py))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_SGD_ITEM_SUMS, (size_t)nitems * (K + 1) * 4 + 256, &pk))) return rc;  // packed item sums + their flags
+  if ((rc = gm_graph_workspace(g, GM_WS_YBITS, nw * 4 * 2 + 64, &pb))) return rc;                       // presence bits: received / applied (+ 64 bytes of scratch)
   float* pack = (float*)pk;
   int32_t* flags = (int32_t*)(pack + (size_t)nitems * K);
   uint32_t* got = (uint32_t*)pb;          // item rows that carry a value from the earlier ranks
@@ -642,8 +642,8 @@ int run_sgd_bipartite(gm_graph_t* g, float* d_latent, const int32_t* d_item_rows
   GM_TRY_HIP(hipEventElapsedTime(&st.total_ms, ev0, ev1));
   st.iterations = iterations;
   g->stats = st;
-  g->note_val[1] = (int64_t)(iterations > 0 ? moved / (unsigned long long)iterations : 0ull);  // bytes received per iteration
-  g->note_set[1] = 1;
+  g->note_val[GM_NOTE_SGD_RING_BYTES] = (int64_t)(iterations > 0 ? moved / (unsigned long long)iterations : 0ull);  // bytes received per iteration
+  g->note_set[GM_NOTE_SGD_RING_BYTES] = 1;
   if (iters_done) *iters_done = iterations;
   return GM_OK;
 }
@@ -654,8 +654,8 @@ int run_rmse_wide(gm_graph_t* g, float* d_latent, hipStream_t s) {
   const int n = d.row_hi - d.row_lo;
   void *px = nullptr, *py = nullptr;
   int rc;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)n * K * 4 + 64, &py))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_X, (size_t)d.ndevice * K * 4 + 64, &px))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_Y, (size_t)n * K * 4 + 64, &py))) return rc;
   const int wgrid = (n + kSgdMulBlock / 64 - 1) / (kSgdMulBlock / 64);
   const int egrid = (int)(((int64_t)n * K + kSgdBlock - 1) / kSgdBlock);
   hipLaunchKernelGGL((k_sgd_send<K>), dim3(egrid), dim3(kSgdBlock), 0, s, (const float*)d_latent,

@@ -21,13 +21,13 @@ int run_fixed(P& prog, gm_graph_t* g, V* d_vp, uint32_t* d_active, int iteration
   }
   void *p0, *p1, *p2, *p3, *p5;
   int rc;
-  if ((rc = gm_graph_workspace(g, 1, (size_t)d.ndevice * sizeof(T) + 16, &p0))) return rc;
-  if ((rc = gm_graph_workspace(g, 2, ((size_t)(d.ndevice + 31) / 32 + 2) * 4, &p1))) return rc;
-  if ((rc = gm_graph_workspace(g, 3, (size_t)rows * sizeof(U) + 16, &p2))) return rc;
-  if ((rc = gm_graph_workspace(g, 4, ((size_t)(rows + 31) / 32 + 2) * 4, &p3))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_X, (size_t)d.ndevice * sizeof(T) + 16, &p0))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_XBITS, ((size_t)(d.ndevice + 31) / 32 + 2) * 4, &p1))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_Y, (size_t)rows * sizeof(U) + 16, &p2))) return rc;
+  if ((rc = gm_graph_workspace(g, GM_WS_YBITS, ((size_t)(rows + 31) / 32 + 2) * 4, &p3))) return rc;
   if (!d_active) {
     const size_t nw = (size_t)(rows + 31) / 32;
-    if ((rc = gm_graph_workspace(g, 5, (nw + 2) * 4, &p5))) return rc;
+    if ((rc = gm_graph_workspace(g, GM_WS_ALL_ACTIVE, (nw + 2) * 4, &p5))) return rc;
     d_active = (uint32_t*)p5;
     hipLaunchKernelGGL(GraphMat::dev::k_fill_u32, dim3(GraphMat::detail::grid_for((int64_t)nw)),
                        dim3(GraphMat::dev::kBlock), 0, s, d_active, (int64_t)nw, 0xffffffffu);

@@ -51,7 +51,7 @@ class MessageExchange:
     def __init__(self, ranges, rank, x_bytes, x_bits, group=None, live_rows=None, x_bytes2=None):
         """live_rows: only the first live_rows entries of every slice need to travel (the
         library's gm_graph_desc_t.xchg_rows); None = whole slices.
-        x_bytes2: second message buffer (adopted as workspace slot 9) for the overlapped two-stage
+        x_bytes2: second message buffer (adopted as workspace slot GM_WS_X2) for the overlapped two-stage
         schedule (GM_XCHG_PART / GM_XCHG_WAIT)."""
         self.ranges = [(int(a), int(b)) for a, b in ranges]
         self.live = None if live_rows is None else int(live_rows)
@@ -291,12 +291,12 @@ def attach_exchange(g, group=None, max_elt_bytes=8, overlap=True):
     x_bytes = torch.zeros(g.ndevice * max_elt_bytes + 64, dtype=torch.uint8, device=g.device)
     x_bits = torch.zeros((g.ndevice + 31) // 32 + 2, dtype=torch.int32, device=g.device)
     L = _lib.lib()
-    _lib.check(L.gm_graph_adopt_workspace(g.h, 1, x_bytes.data_ptr(), x_bytes.numel()))
-    _lib.check(L.gm_graph_adopt_workspace(g.h, 2, x_bits.data_ptr(), x_bits.numel() * 4))
+    _lib.check(L.gm_graph_adopt_workspace(g.h, _lib.GM_WS_X, x_bytes.data_ptr(), x_bytes.numel()))
+    _lib.check(L.gm_graph_adopt_workspace(g.h, _lib.GM_WS_XBITS, x_bits.data_ptr(), x_bits.numel() * 4))
     x_bytes2 = None
     if overlap:
         x_bytes2 = torch.zeros(g.ndevice * max_elt_bytes + 64, dtype=torch.uint8, device=g.device)
-        _lib.check(L.gm_graph_adopt_workspace(g.h, 9, x_bytes2.data_ptr(), x_bytes2.numel()))
+        _lib.check(L.gm_graph_adopt_workspace(g.h, _lib.GM_WS_X2, x_bytes2.data_ptr(), x_bytes2.numel()))
     ex = MessageExchange(ranges, rank, x_bytes, x_bits, group, live_rows=g.xchg_rows, x_bytes2=x_bytes2)
     cb = ex.callback()
     g._cb = (cb, ex)  # keep alive

@@ -414,12 +414,17 @@ void Graph<V, E>::ReadEdgelist(GraphMat::edgelist_t<E> A_edges) {
     // the push step's bid and list arrays): allocated here so the first run does not pay hipMalloc
     void* p = nullptr;
     const size_t n = (size_t)d.ndevice, words = ((n + 31) / 32 + 2) * 4;
-    const size_t want[GM_WS_SLOTS] = {4096, n * 8 + 16, words, n * 8 + 16, words, 0, n * 8 + 64, n * 4 + 64};
+    size_t want[GM_WS_SLOTS] = {0};
+    want[GM_WS_FLAGS] = 4096;
+    want[GM_WS_X] = want[GM_WS_Y] = n * 8 + 16;
+    want[GM_WS_XBITS] = want[GM_WS_YBITS] = words;
+    want[GM_WS_PUSH_BIDS] = n * 8 + 64;
+    want[GM_WS_ACTIVE_LIST] = n * 4 + 64;
     for (int slot = 0; slot < GM_WS_SLOTS; slot++)
       if (want[slot]) (void)gm_graph_workspace(A, slot, want[slot], &p);
     // the first launch of one of the engine's kernels makes the HIP runtime resolve this
     // executable's kernel table (~8 ms measured with the reference's BFS.cpp): pay it here
-    if (gm_graph_workspace(A, 0, 4096, &p) == GM_OK) {
+    if (gm_graph_workspace(A, GM_WS_FLAGS, 4096, &p) == GM_OK) {
       hipLaunchKernelGGL(dev::k_fill_u32, dim3(1), dim3(dev::kBlock), 0, 0, (uint32_t*)p, (int64_t)64, 0u);
       (void)hipDeviceSynchronize();
     }
@@ -657,7 +662,7 @@ const V* Graph<V, E>::gathered_vertexproperty() {
   gm_graph_desc_t d;
   gm_graph_desc(A, &d);
   void* buf = nullptr;
-  if (gm_graph_workspace(A, 13, (size_t)d.ndevice * sizeof(V) + 64, &buf) != GM_OK) { printf("GraphMat(HIP): %s\n", gm_last_error()); exit(1); }
+  if (gm_graph_workspace(A, GM_WS_VPROP_STAGE, (size_t)d.ndevice * sizeof(V) + 64, &buf) != GM_OK) { printf("GraphMat(HIP): %s\n", gm_last_error()); exit(1); }
   const int rows = d.row_hi - d.row_lo;
   vertexproperty->segment->need_device();
   GM_HIP_OK(hipMemcpy((char*)buf + (size_t)d.row_lo * sizeof(V), vertexproperty->segment->value, (size_t)rows * sizeof(V), hipMemcpyDeviceToDevice));

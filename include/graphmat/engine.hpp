@@ -284,6 +284,29 @@ constexpr bool wave16_ok() {
          (sizeof(U) == 4 || sizeof(U) == 8);
 }
 
+// The run's flag / statistics block: 4096 bytes of device scratch (workspace slot GM_WS_FLAGS) and the graph's pinned host mirror
+// (gm_graph_run_resources), which has the same layout.  Offsets in bytes.  The changed flag sits directly in front of the striped
+// statistics, so that one memset clears and one copy fetches "flag + statistics": every call the host makes between two short levels of a
+// traversal shows up as idle time on the GPU.
+struct FlagBlock {
+  static constexpr size_t kBytes = 4096;
+  static constexpr size_t kListCount = 8;      // u32: entries of the active-set list (when the set is small)
+  static constexpr size_t kTouchedCount = 12;  // u32: entries of the touched list (destinations bid for in a top-down step)
+  static constexpr size_t kStats = 16;         // 3 x u64: vertices, out-edges, largest out-degree of the first active set (k_frontier_stats)
+  static constexpr size_t kChanged = 508;      // int: the changed flag
+  static constexpr size_t kStriped = 512;      // kStatSlots x 4 u64: the next active set's statistics (k_apply, k_push_finish)
+  static constexpr size_t kStripedBytes = (size_t)dev::kStatSlots * 4 * sizeof(unsigned long long);
+  static constexpr size_t kProbeMismatch = 2800;  // u32: sampled rows that differ from the ordered fold (k_check_rows)
+  static constexpr size_t kSpecOff = 2880;        // int32: a speculation on the giant rows failed its proof (Launch::spec_off)
+  template <class F>
+  static F* at(void* block, size_t offset) { return (F*)((char*)block + offset); }
+};
+static_assert(FlagBlock::kListCount + 4 <= FlagBlock::kTouchedCount && FlagBlock::kTouchedCount + 4 <= FlagBlock::kStats && FlagBlock::kStats + 24 <= FlagBlock::kChanged,
+              "FlagBlock: counters and first statistics overlap");
+static_assert(FlagBlock::kChanged + sizeof(int) == FlagBlock::kStriped, "FlagBlock: the changed flag sits directly in front of the striped statistics");
+static_assert(FlagBlock::kStriped + FlagBlock::kStripedBytes <= FlagBlock::kProbeMismatch && FlagBlock::kProbeMismatch + 4 <= FlagBlock::kSpecOff &&
+              FlagBlock::kSpecOff + 4 <= FlagBlock::kBytes, "FlagBlock: fields overlap or leave the block");
+
 // what a multiply pass is launched with: the graph (scratch, tiles), the run's stream, the options of this run, and where to
 // account launches and phase times; `aux` = the auxiliary stream's state or null
 struct Launch {
@@ -300,22 +323,326 @@ struct Launch {
                                // giant rows are replayed as float sums and every chunk is PROVEN with the program's own function (k_giant_verify_chunks)
 };
 
-// one multiply+reduce pass over one direction of the adjacency, strategy RK
+// f launches the HAS_VALS = true / false form of a kernel: f(std::true_type()) when the structure at hand carries edge values (`have`) of a
+// type the sweep, the column-blocked stream and the sliced gather can hold -- the true form is only instantiated for such an E
+template <class E, class F>
+void with_edge_values(bool have, F&& f) {
+  if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
+    if (have) return f(std::true_type());
+  }
+  f(std::false_type());
+}
+// ... and the same idiom for a kernel's 2- / 3-operand form (USE_VP), chosen at run time
+template <class F>
+void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type()); else f(std::false_type());
+}
+
+// ---- one multiply+reduce pass over one direction of the adjacency, strategy RK --------------------------------------------
+constexpr int kWavesPerBlock = dev::kBlock / 64;  // rows (waves) per workgroup of the one-wave-per-row kernels
+inline unsigned wave_grid(int rows) { return (unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock); }
+
+// ---- the giant rows ------------------------------------------------------------------------------------------------------
+// Workspace slot GM_WS_SPECULATION, the records of a speculated pass over the giant rows: [chunk boundaries (float sum) or running values
+// per chunk (any function), 8 bytes each, ngchunk + 2 of them][redo flag per giant row] -- apps/speculated_float_sum.cpp and
+// tests/test_gpu_parity.py read these two -- then the arrays of the any-function proof.  Offsets in bytes.
+struct SpecLayout { size_t redo, bhas, tval, thas, fin, finhas, bytes; };
+inline SpecLayout spec_layout(int ngchunk, int ngiant) {
+  auto pad8 = [](size_t bytes) { return (bytes + 7) & ~(size_t)7; };
+  SpecLayout o;
+  o.redo = ((size_t)ngchunk + 2) * 8;
+  o.bhas = o.redo + pad8((size_t)ngiant * 4);
+  o.tval = o.bhas + pad8((size_t)ngchunk * 4);
+  o.thas = o.tval + (size_t)ngchunk * 8;
+  o.fin = o.thas + pad8((size_t)ngchunk * 4);
+  o.finhas = o.fin + (size_t)ngiant * 8;
+  o.bytes = o.finhas + (size_t)ngiant * 4 + 64;
+  return o;
+}
+
+// The operands of a pass and its three parts: the giant rows, the short rows, the wave rows (launch_spmv_rk, below, decides their streams).
 template <class P, class T, class U, class V, class E, bool USE_VP, int RK>
-void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& A_in, const T* x, const uint32_t* xbits,
-                    const V* vp, U* y, uint32_t* ybits, int accumulate, const uint32_t* want = nullptr, bool grouped = false,
-                    const uint32_t* xsum = nullptr) {
-  constexpr int WPB = dev::kBlock / 64;  // rows (waves) per workgroup of k_spmv_wave
-  gm_graph_t* const g = L.g;
-  const hipStream_t s = L.s;
-  int* const launches = L.launches;
-  PhaseTimer* const timer = L.timer;
-  AuxStream* const aux = L.aux;
+struct SpmvPass {
+  const Launch& L;
+  const dev::ProgArg<P>& pa;
+  const gm_csr_t& A;
+  const T* x;
+  const uint32_t* xbits;
+  const V* vp;
+  U* y;
+  uint32_t* ybits;
+  int accumulate;
+  const uint32_t* want;
+  bool grouped;
+  const uint32_t* xsum;
+  void launched() const { (*L.launches)++; }  // (gm_run_stats_t.spmv_launches: called once per kernel, next to its launch)
+
+  // the giant rows' products stream and, over a sparse x, its presence bits (the pointers stay null where the graph cannot give the scratch)
+  bool giant_products(bool sparse_x, U** terms, unsigned long long** tpres) const {
+    void *pt = nullptr, *pp = nullptr;
+    if (gm_graph_workspace(L.g, GM_WS_GIANT_TERMS, (size_t)A.giant_edges * sizeof(U) + 64, &pt) != GM_OK) return false;
+    *terms = (U*)pt;
+    if (sparse_x && gm_graph_workspace(L.g, GM_WS_GIANT_TPRES, (size_t)A.giant_edges / 8 + 64, &pp) != GM_OK) return false;
+    *tpres = (unsigned long long*)pp;
+    return true;
+  }
+  // Put the products of all giant-row edges into the stream, spread over the whole chip -- unless they are there already (Launch::terms_ready:
+  // the sweep gathered them).  The one place k_giant_terms is launched.
+  void giant_terms(hipStream_t gs, U* terms, unsigned long long* tpres, dev::gchunk_state* maps) const {
+    if (L.terms_ready) return;
+    hipLaunchKernelGGL((dev::k_giant_terms<P, T, U, V, E, USE_VP>), dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, pa, A, x, xbits, vp, terms, tpres
+                       GM_DBG_ARG(L.opt.debug_flags), maps);
+    launched();
+  }
+  // Sums, maps, replay with maps (kernels.hpp: gchunk_state): the sub-pieces' maps for the binades predicted from this pass's products, then one
+  // wave per row walks them: the exact replay of a float sum, its serial part limited to the binade crossings (bounds / spec_off: speculation only)
+  void giant_replay_with_maps(hipStream_t gs, const U* terms, dev::gchunk_state* maps, unsigned long long* bounds, const int32_t* spec_off) const {
+    hipLaunchKernelGGL(dev::k_giant_sums, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps);
+    launched();
+    hipLaunchKernelGGL(dev::k_giant_maps, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps, (const float*)y, (const uint32_t*)ybits, accumulate);
+    launched();
+    hipLaunchKernelGGL((dev::k_giant_replay_maps<P, U>), dim3(A.ngiant), dim3(64), 0, gs, pa, A, y, ybits, accumulate, terms, (const dev::gchunk_state*)maps, bounds, spec_off);
+    launched();
+  }
+  // a workgroup per giant row, strategy RK (terms / tpres: the products stream, or null: the kernel gathers by itself)
+  template <int K>
+  void giant_block_per_row(hipStream_t gs, const U* terms, const unsigned long long* tpres, unsigned long long* bounds, const int32_t* spec_off) const {
+    hipLaunchKernelGGL((dev::k_spmv_giant<P, T, U, V, E, USE_VP, K>), dim3(A.ngiant), dim3(dev::kGiant), 0, gs, pa, A, x, xbits, vp, y, ybits,
+                       accumulate GM_DBG_ARG(L.opt.debug_flags), terms, tpres, want, (dev::gchunk_state*)nullptr, bounds, spec_off);
+    launched();
+  }
+  // one wave per row folds the dense products stream in stored order (only: null, or per giant row whether to fold it)
+  void giant_fold_ordered(hipStream_t gs, const U* terms, const unsigned long long* tpres, const int32_t* only, const int32_t* spec_off) const {
+    hipLaunchKernelGGL((dev::k_giant_fold_ordered<P, U, V>), dim3(wave_grid(A.ngiant)), dim3(dev::kBlock), 0, gs, pa, A, vp, y, ybits, accumulate, terms, tpres, want, only, spec_off);
+    launched();
+  }
+
+  // Strategy: a DECLARED float sum.  The exact replay -- with piece maps (float sums over a dense x, every row wanted) or a workgroup per row.
+  void giant_rows_float_sum(hipStream_t gs) const {
+    U* terms = nullptr;
+    unsigned long long* tpres = nullptr;
+    dev::gchunk_state* maps = nullptr;
+    giant_products(xbits != nullptr, &terms, &tpres);
+    if constexpr (std::is_same<U, float>::value) {
+      if (xbits == nullptr && want == nullptr && L.opt.giant_maps != 0) maps = (dev::gchunk_state*)A.gchunk_state;
+    }
+    giant_terms(gs, terms, tpres, maps);
+    if constexpr (std::is_same<U, float>::value) {
+      if (maps != nullptr) return giant_replay_with_maps(gs, terms, maps, nullptr, nullptr);
+    }
+    giant_block_per_row<REDUCE_F32_ADD>(gs, terms, tpres, nullptr, nullptr);
+  }
+
+  // The two strategies below SPECULATE on a reduce_function nothing is declared about and PROVE the result chunk by chunk with the function
+  // itself (kernels.hpp: k_giant_verify_chunks / k_giant_verify_chunks_any); rows with a disagreeing chunk are folded again in order.  They
+  // take whole rows only (nothing in y to start from), and a failed proof switches them off for the rest of the run (Launch::spec_off).
+  bool may_speculate() const {
+    return L.opt.ordered_giant_two_pass >= 2 && L.spec_off != nullptr && !(accumulate & dev::ACC_READ_PREV) && A.gchunk_row != nullptr;
+  }
+  // Strategy: a float sum BY ITS ANSWERS (Launch::guess_f32_add), a dense x, every row wanted: the exact replay, proven chunk by chunk.
+  bool giant_rows_proven_float_sum(hipStream_t gs) const {
+    if constexpr (std::is_same<U, float>::value) {
+      const SpecLayout lay = spec_layout(A.ngchunk, A.ngiant);
+      U* terms = nullptr;
+      unsigned long long* tpres = nullptr;
+      void* rec = nullptr;
+      if (!(may_speculate() && L.guess_f32_add && xbits == nullptr && want == nullptr && giant_products(false, &terms, &tpres) &&
+            gm_graph_workspace(L.g, GM_WS_SPECULATION, lay.bytes, &rec) == GM_OK))
+        return false;
+      unsigned long long* bounds = (unsigned long long*)rec;
+      int32_t* redo = (int32_t*)((char*)rec + lay.redo);
+      dev::gchunk_state* maps = L.opt.giant_maps != 0 ? (dev::gchunk_state*)A.gchunk_state : nullptr;
+      GM_HIP_OK(hipMemsetAsync(redo, 0, (size_t)A.ngiant * 4, gs));
+      giant_terms(gs, terms, nullptr, maps);
+      if (maps != nullptr) giant_replay_with_maps(gs, terms, maps, bounds, L.spec_off);
+      else giant_block_per_row<REDUCE_F32_ADD>(gs, terms, nullptr, bounds, L.spec_off);
+      hipLaunchKernelGGL((dev::k_giant_verify_chunks<P, U>), dim3(wave_grid(A.ngchunk)), dim3(dev::kBlock), 0, gs, pa, A, terms, bounds, y, redo, L.spec_off);
+      launched();
+      giant_fold_ordered(gs, terms, nullptr, redo, L.spec_off);
+      return true;
+    }
+    return false;
+  }
+  // Strategy: ANY function, speculated to be associative on the operands at hand (chunk totals give candidates for the running values)
+  bool giant_rows_proven_any(hipStream_t gs) const {
+    if constexpr (dev::stageable<U>::value && std::is_trivially_copyable<U>::value && (sizeof(U) == 4 || sizeof(U) == 8)) {
+      const SpecLayout lay = spec_layout(A.ngchunk, A.ngiant);
+      U* terms = nullptr;
+      unsigned long long* tpres = nullptr;
+      void* rec = nullptr;
+      if (!(may_speculate() && giant_products(xbits != nullptr, &terms, &tpres) && gm_graph_workspace(L.g, GM_WS_SPECULATION, lay.bytes, &rec) == GM_OK))
+        return false;
+      char* w = (char*)rec;
+      U *bval = (U*)w, *tval = (U*)(w + lay.tval), *fin = (U*)(w + lay.fin);
+      int32_t *redo = (int32_t*)(w + lay.redo), *bhas = (int32_t*)(w + lay.bhas), *thas = (int32_t*)(w + lay.thas), *finhas = (int32_t*)(w + lay.finhas);
+      const unsigned cgrid = wave_grid(A.ngchunk), rgrid = wave_grid(A.ngiant);
+      GM_HIP_OK(hipMemsetAsync(redo, 0, (size_t)A.ngiant * 4, gs));
+      giant_terms(gs, terms, tpres, nullptr);
+      hipLaunchKernelGGL((dev::k_giant_chunk_totals<P, U, V>), dim3(cgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, terms, tpres, tval, thas, L.spec_off);
+      launched();
+      hipLaunchKernelGGL((dev::k_giant_chunk_scan<P, U, V>), dim3(rgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, y, ybits, accumulate, tval, thas, bval, bhas, fin, finhas, L.spec_off);
+      launched();
+      hipLaunchKernelGGL((dev::k_giant_verify_chunks_any<P, U, V>), dim3(cgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, terms, tpres, bval, bhas, fin, finhas, redo, L.spec_off);
+      launched();
+      giant_fold_ordered(gs, terms, tpres, redo, L.spec_off);
+      return true;
+    }
+    return false;
+  }
+  // Strategy: the plain two-pass ordered fold: products spread over the chip, then one wave per row folds them in stored order
+  bool giant_rows_two_pass(hipStream_t gs) const {
+    if constexpr (dev::stageable<U>::value && std::is_trivially_copyable<U>::value) {
+      U* terms = nullptr;
+      unsigned long long* tpres = nullptr;
+      if (!(L.opt.ordered_giant_two_pass != 0 && giant_products(xbits != nullptr, &terms, &tpres))) return false;
+      giant_terms(gs, terms, tpres, nullptr);
+      giant_fold_ordered(gs, terms, tpres, nullptr, nullptr);
+      return true;
+    }
+    return false;
+  }
+  // Strategy: one wave per row that gathers by itself (always correct; what larger reduction types keep)
+  void giant_rows_one_wave(hipStream_t gs) const {
+    hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, REDUCE_ORDERED>), dim3(wave_grid(A.ngiant)), dim3(dev::kBlock), 0, gs, pa, A, A.giant_row, A.ngiant, x,
+                       xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+    launched();
+  }
+  // The giant rows: a workgroup each when the reduction kind has a block-wide strategy, otherwise the first ordered strategy that takes them
+  void giant_rows(hipStream_t gs) const {
+    if constexpr (RK == REDUCE_F32_ADD && sizeof(U) == 4) {
+      giant_rows_float_sum(gs);
+    } else if constexpr ((RK == REDUCE_COMMUTATIVE || RK == REDUCE_LAST) && sizeof(U) <= 8) {
+      giant_block_per_row<RK>(gs, nullptr, nullptr, nullptr, nullptr);
+    } else {
+      if (giant_rows_proven_float_sum(gs)) return;
+      if (giant_rows_proven_any(gs)) return;
+      if (giant_rows_two_pass(gs)) return;
+      giant_rows_one_wave(gs);
+    }
+  }
+
+  // ---- the short rows: row-blocks, or one lane per row for a=b programs, or persistent workgroups that take row-blocks by waves ----------
+  void short_rows(bool keep) const {
+    // (a run-time test of RK: the row-block kernels below are instantiated for a=b programs as well, as they always were)
+    if (RK == REDUCE_LAST) {
+      // a=b: one lane per row over the whole row range (short rows pick themselves by their length)
+      if constexpr (RK == REDUCE_LAST) {
+        hipLaunchKernelGGL((dev::k_spmv_short_last<P, T, U, V, E, USE_VP>), dim3(grid_for(A.nrows)), dim3(dev::kBlock), 0, L.s, pa, A, x, xbits, vp, y, ybits,
+                           accumulate GM_DBG_ARG(L.opt.debug_flags), want, xsum);
+        launched();
+      }
+      return;
+    }
+    if constexpr (!USE_VP && sizeof(T) == 4 && sizeof(U) == 4 && RK != REDUCE_LAST && std::is_trivially_copyable<T>::value) {
+      // persistent workgroups sharing a large LDS hot set, row-blocks taken by waves (kernels.hpp: k_spmv_rowwave)
+      const int form = L.opt.rowwave_form & 15;
+      const bool any_size = (L.opt.rowwave_form & 16) != 0;  // (tests: also for small graphs)
+      const bool whole_cols = A.hot_base == 0 && A.hot_len >= A.ncols;  // (not a column tile: the untiled pass of a tiled graph, or an untiled graph)
+      // (1024 threads / 30720 entries: the row-block time falls by 15 % but the kernels of the auxiliary stream find no
+      // LDS next to it and the iteration gains nothing; 20480 entries leave them room; 512 / 16384 and 256 / 8192: no gain)
+      if (form == 4 && xbits == nullptr && want == nullptr && !program_row_filter<P>::enabled && (persistent_forms_pay(A) || any_size) &&
+          !(whole_cols && (keep || L.tiled_untiled_pass) && L.opt.untiled_pass_plain != 0)) {
+        constexpr int BLOCK = 1024, HOT = 20480;
+        const int fit = 1;  // (workgroups of this size that fit a CU)
+        const int per_cu = L.opt.persist_per_cu > 0 && L.opt.persist_per_cu < fit ? L.opt.persist_per_cu : fit;
+        int grid = cu_count() * per_cu;
+        const int need = (A.nblk + BLOCK / 64 - 1) / (BLOCK / 64);
+        if (grid > need) grid = need;
+        hipLaunchKernelGGL((dev::k_spmv_rowwave<P, T, U, V, E, BLOCK, HOT>), dim3(grid), dim3(BLOCK), 0, L.s, pa, A, x, y, ybits, accumulate);
+        launched();
+        return;
+      }
+    }
+    if (xbits == nullptr)
+      hipLaunchKernelGGL((dev::k_spmv_rowblock<P, T, U, V, E, USE_VP, true, RK>), dim3(A.nblk), dim3(dev::kBlock), 0, L.s, pa, A, x, xbits, vp, y, ybits,
+                         accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+    else
+      hipLaunchKernelGGL((dev::k_spmv_rowblock<P, T, U, V, E, USE_VP, false, RK>), dim3(A.nblk), dim3(dev::kBlock), 0, L.s, pa, A, x, xbits, vp, y, ybits,
+                         accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+    launched();
+  }
+
+  // ---- the wave rows: a wave per row, 16 rows per wave for ordered folds, or 64 list entries per wave under a row bitmap --------------------
+  // long_on_aux: the long rows at the head of the list go to the auxiliary stream (fork_aux() forks it off the run's stream once per pass)
+  template <class Fork>
+  void wave_rows(bool long_on_aux, Fork&& fork_aux) const {
+    const hipStream_t s = L.s;
+    PhaseTimer* const timer = L.timer;
+    AuxStream* const aux = L.aux;
+    if (grouped && want != nullptr) {  // a row bitmap governs: 64 list entries per wave, only the wanted rows are worked on
+      const int groups = (A.nmid + 63) / 64;
+      // (running this kernel on the auxiliary stream next to the short rows' kernel was measured: both want every wave
+      // slot of the chip, side by side each takes twice as long -- RMAT-26, first bottom-up level: 1.55 against 1.52 ms)
+      bool done = false;
+      if constexpr (RK == REDUCE_LAST) {
+        if (L.opt.last_rows_lanes == 16) {
+          hipLaunchKernelGGL((dev::k_spmv_wave_grouped<P, T, U, V, E, USE_VP, RK, 16>), dim3(wave_grid(groups)), dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits,
+                             vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want, xsum);
+          done = true;
+        }
+      }
+      if (!done)
+        hipLaunchKernelGGL((dev::k_spmv_wave_grouped<P, T, U, V, E, USE_VP, RK>), dim3(wave_grid(groups)), dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits, vp,
+                           y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want, xsum);
+    } else if (wave16_ok<U, USE_VP, RK>() && !(L.opt.debug_flags & dev::DBG_NO_WAVE16)) {
+      if constexpr (wave16_ok<U, USE_VP, RK>()) {
+        // ordered folds: the long rows at the head of the list get a wave each, the rest are folded 16 to a wave
+        const int nlong = A.nmid_long < A.nmid ? A.nmid_long : A.nmid;
+        const int rest = A.nmid - nlong;
+        const int groups = (rest + dev::kWaveRows - 1) / dev::kWaveRows;
+        // the long rows: a wave each (k_spmv_wave), on the auxiliary stream during column-tile passes.  (Handing them to
+        // the waves of the persistent kernel below -- one launch, long rows first off the same work counter -- was
+        // measured at RMAT-26: 6.6 -> 7.9 ms per iteration.  wave_row's ordered fold is a serial chain per wave and wants
+        // the 32 waves per CU the plain kernel gets, not the 16 of a workgroup that holds 90 KB of LDS.)
+        if (nlong > 0) {
+          hipStream_t ls = s;
+          if (long_on_aux) {
+            fork_aux();
+            ls = aux->s;
+            if (timer) timer->aux_mark(ls);
+          }
+          hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, RK>), dim3(wave_grid(nlong)), dim3(dev::kBlock), 0, ls, pa, A, A.mid_row, nlong, x, xbits, vp, y,
+                             ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+          if (long_on_aux) {
+            if (timer) timer->aux_mark(ls);
+            GM_HIP_OK(hipEventRecord(aux->join, ls));  // (re-recorded behind the giant passes' record: the wait of launch_spmv_rk sees this one)
+          }
+        }
+        // Large graphs: the 16-row groups go to persistent 1024-thread workgroups that load the slice's 22528 busiest x
+        // entries into LDS once, their waves taking groups in an interleaved order (kernels.hpp: k_spmv_wave16p; measured
+        // in profiles/r03_persistent_kernels.md)
+        bool done = false;
+        if constexpr (sizeof(T) == 4 && sizeof(U) == 4) {
+          const int form = persistent_forms_pay(A) || (L.opt.wave16_form & 16) ? (L.opt.wave16_form & 15) : 0;
+          if (rest > 0 && form == 2) {
+            constexpr int BLOCK = 1024, HOT = 22528;
+            int grid = cu_count();
+            const int need = (groups + BLOCK / 64 - 1) / (BLOCK / 64);
+            if (grid > need) grid = need;
+            hipLaunchKernelGGL((dev::k_spmv_wave16p<P, T, U, V, E, BLOCK, HOT>), dim3(grid), dim3(BLOCK), 0, s, pa, A, A.mid_row + nlong, rest, x, xbits, vp, y, ybits,
+                               accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+            done = true;
+          }
+        }
+        if (!done && rest > 0) {
+          constexpr int W16 = dev::kWave16Block / 64;
+          hipLaunchKernelGGL((dev::k_spmv_wave16<P, T, U, V, E>), dim3((groups + W16 - 1) / W16), dim3(dev::kWave16Block), 0, s, pa, A, A.mid_row + nlong, rest, x, xbits, vp,
+                             y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+        }
+      }
+    } else
+      hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, RK>), dim3(wave_grid(A.nmid)), dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits, vp, y,
+                         ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
+    launched();  // (the wave rows count as one launch, however many kernels share them)
+  }
+
 #ifdef GRAPHMAT_ABLATION
-  gm_csr_t A = A_in;
-  {
+  // ablation builds: the pass's view of the adjacency with the "cold from" column of this run's options, and -- once per view -- a count of
+  // the edges it makes cold
+  static gm_csr_t ablation_view(const Launch& L, const gm_csr_t& A_in) {
+    gm_csr_t A = A_in;
     int ntile = 1;
-    gm_graph_tiles(g, GM_DIR_OUT, &ntile);
+    gm_graph_tiles(L.g, GM_DIR_OUT, &ntile);
     const bool whole = A.hot_base == 0 && A.hot_len >= A.ncols;
     A.cold_from = (whole && ntile > 1) ? -L.opt.ablate_cold_short : L.opt.ablate_cold_from;
     static std::vector<const void*> seen;
@@ -328,7 +655,7 @@ void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& 
         for (int t = 0; t < ntile; t++) {
           gm_csr_t At;
           const uint32_t* prev = nullptr;
-          if (gm_graph_tile(g, GM_DIR_OUT, t, &At, &prev) == GM_OK) base[t] = At.hot_base;
+          if (gm_graph_tile(L.g, GM_DIR_OUT, t, &At, &prev) == GM_OK) base[t] = At.hot_base;
         }
         GM_HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(dev::g_abl_tile_base), base, sizeof(base)));
         GM_HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(dev::g_abl_ntiles), &ntile, sizeof(int)));
@@ -337,17 +664,33 @@ void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& 
       unsigned long long h_n = 0;
       GM_HIP_OK(hipMalloc(&d_n, 8));
       GM_HIP_OK(hipMemset(d_n, 0, 8));
-      hipLaunchKernelGGL(dev::k_abl_count, dim3(4096), dim3(256), 0, s, A.colidx, (int64_t)A.nnz, A.cold_from, A.hot_base, d_n);
-      GM_HIP_OK(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, s));
-      GM_HIP_OK(hipStreamSynchronize(s));
+      hipLaunchKernelGGL(dev::k_abl_count, dim3(4096), dim3(256), 0, L.s, A.colidx, (int64_t)A.nnz, A.cold_from, A.hot_base, d_n);
+      GM_HIP_OK(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, L.s));
+      GM_HIP_OK(hipStreamSynchronize(L.s));
       GM_HIP_OK(hipFree(d_n));
       printf("GraphMat(HIP) ablation: view base %d len %d: %lld edges, %llu cold (cold_from %d)\n", A.hot_base, A.hot_len, (long long)A.nnz, h_n, A.cold_from);
     }
+    return A;
   }
+#endif
+};
+
+// one multiply+reduce pass over one direction of the adjacency, strategy RK: the giant rows (on the auxiliary stream when there is something
+// to overlap them with), the short rows, the wave rows
+template <class P, class T, class U, class V, class E, bool USE_VP, int RK>
+void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& A_in, const T* x, const uint32_t* xbits,
+                    const V* vp, U* y, uint32_t* ybits, int accumulate, const uint32_t* want = nullptr, bool grouped = false,
+                    const uint32_t* xsum = nullptr) {
+#ifdef GRAPHMAT_ABLATION
+  const gm_csr_t A = SpmvPass<P, T, U, V, E, USE_VP, RK>::ablation_view(L, A_in);
 #else
   const gm_csr_t& A = A_in;
 #endif
   if (A.nnz == 0) return;
+  const SpmvPass<P, T, U, V, E, USE_VP, RK> p{L, pa, A, x, xbits, vp, y, ybits, accumulate, want, grouped, xsum};
+  const hipStream_t s = L.s;
+  PhaseTimer* const timer = L.timer;
+  AuxStream* const aux = L.aux;
   const bool defer = aux != nullptr && aux->s != nullptr && aux->defer;
   const bool keep = aux != nullptr && aux->s != nullptr && aux->keep;
   const bool overlap = aux != nullptr && aux->s != nullptr && A.ngiant > 0 && (defer || keep || A.nblk > 0 || A.nmid > 0);
@@ -375,145 +718,7 @@ void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& 
       gs = aux->s;
       if (timer) timer->aux_mark(gs);
     }
-    // giant rows: a workgroup each when the reduction kind has a block-wide strategy,
-    // otherwise the ordered wave fold (always correct)
-    if constexpr ((RK == REDUCE_F32_ADD && sizeof(U) == 4) ||
-                  ((RK == REDUCE_COMMUTATIVE || RK == REDUCE_LAST) && sizeof(U) <= 8)) {
-      U* terms = nullptr;
-      unsigned long long* tpres = nullptr;
-      dev::gchunk_state* maps = nullptr;
-      if constexpr (RK == REDUCE_F32_ADD) {
-        // pass 1: products of all giant-row edges, spread over the whole chip
-        void *p6 = nullptr, *p7 = nullptr;
-        gm_graph_workspace(g, 6, (size_t)A.giant_edges * sizeof(U) + 64, &p6);
-        terms = (U*)p6;
-        if (xbits != nullptr) {
-          gm_graph_workspace(g, 14, (size_t)A.giant_edges / 8 + 64, &p7);  // (slot 7 holds the active-set list of sharded ACTIVE_ONLY runs)
-          tpres = (unsigned long long*)p7;
-        }
-        // piece maps (kernels.hpp: gchunk_state): the exact replay of a giant row spread over the whole chip, its serial
-        // part limited to the binade crossings.  float sums over a dense x only.
-        if constexpr (std::is_same<U, float>::value) {
-          if (xbits == nullptr && want == nullptr && L.opt.giant_maps != 0) maps = (dev::gchunk_state*)A.gchunk_state;
-        }
-        if (L.terms_ready) {
-          // (the products are in the stream already -- the sweep gathered them: nothing to do here)
-        } else {
-          hipLaunchKernelGGL((dev::k_giant_terms<P, T, U, V, E, USE_VP>), dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, pa, A, x, xbits, vp, terms, tpres
-                             GM_DBG_ARG(L.opt.debug_flags), maps);
-          (*launches)++;
-        }
-      }
-      bool replayed = false;
-      if constexpr (RK == REDUCE_F32_ADD && std::is_same<U, float>::value) {
-        if (maps != nullptr) {  // the sub-pieces' maps for the binades predicted from this pass's products, then one wave per row walks them (kernels.hpp: gchunk_state)
-          hipLaunchKernelGGL(dev::k_giant_sums, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps);
-          hipLaunchKernelGGL(dev::k_giant_maps, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps, (const float*)y, (const uint32_t*)ybits, accumulate);
-          hipLaunchKernelGGL((dev::k_giant_replay_maps<P, U>), dim3(A.ngiant), dim3(64), 0, gs, pa, A, y, ybits, accumulate, (const U*)terms, (const dev::gchunk_state*)maps,
-                             (unsigned long long*)nullptr, (const int32_t*)nullptr);
-          (*launches) += 2;
-          replayed = true;
-        }
-      }
-      if (!replayed)
-        hipLaunchKernelGGL((dev::k_spmv_giant<P, T, U, V, E, USE_VP, RK>), dim3(A.ngiant), dim3(dev::kGiant), 0, gs, pa,
-                           A, x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), (const U*)terms,
-                           (const unsigned long long*)tpres, want, (dev::gchunk_state*)nullptr);
-    } else {
-      // plain ordered fold (any reduce_function): products spread over the chip by k_giant_terms, then one wave per row
-      // folds the dense products stream in stored order (kernels.hpp: k_giant_fold_ordered).  Larger reduction types keep
-      // the one-wave-per-row kernel that gathers by itself.
-      bool two_pass = false;
-      // speculate-and-prove (kernels.hpp: k_giant_verify_chunks / k_giant_verify_chunks_any): the whole rows, nothing in y to start from
-      const bool may_speculate = L.opt.ordered_giant_two_pass >= 2 && L.spec_off != nullptr && !(accumulate & dev::ACC_READ_PREV) && A.gchunk_row != nullptr;
-      // workspace slot 15: [chunk boundaries, 8 bytes each][redo flag per giant row] (apps/speculated_float_sum.cpp reads these two), then the other arrays
-      const size_t o_redo = ((size_t)A.ngchunk + 2) * 8, o_bhas = o_redo + (((size_t)A.ngiant * 4 + 7) & ~(size_t)7), o_tval = o_bhas + (((size_t)A.ngchunk * 4 + 7) & ~(size_t)7),
-                   o_thas = o_tval + (size_t)A.ngchunk * 8, o_fin = o_thas + (((size_t)A.ngchunk * 4 + 7) & ~(size_t)7), o_finhas = o_fin + (size_t)A.ngiant * 8,
-                   o_end = o_finhas + (size_t)A.ngiant * 4 + 64;
-      if constexpr (std::is_same<U, float>::value) {
-        // a float sum by its answers, a dense x, every row wanted: the exact replay, proven chunk by chunk
-        void *p6 = nullptr, *p15 = nullptr;
-        if (may_speculate && L.guess_f32_add && xbits == nullptr && want == nullptr &&
-            gm_graph_workspace(g, 6, (size_t)A.giant_edges * sizeof(U) + 64, &p6) == GM_OK && gm_graph_workspace(g, 15, o_end, &p15) == GM_OK) {
-          U* terms = (U*)p6;
-          unsigned long long* bounds = (unsigned long long*)p15;
-          int32_t* redo = (int32_t*)((char*)p15 + o_redo);
-          dev::gchunk_state* maps = L.opt.giant_maps != 0 ? (dev::gchunk_state*)A.gchunk_state : nullptr;
-          GM_HIP_OK(hipMemsetAsync(redo, 0, (size_t)A.ngiant * 4, gs));
-          if (!L.terms_ready) {
-            hipLaunchKernelGGL((dev::k_giant_terms<P, T, U, V, E, USE_VP>), dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, pa, A, x, xbits, vp, terms,
-                               (unsigned long long*)nullptr GM_DBG_ARG(L.opt.debug_flags), maps);
-            (*launches)++;
-          }
-          if (maps != nullptr) {
-            hipLaunchKernelGGL(dev::k_giant_sums, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps);
-            hipLaunchKernelGGL(dev::k_giant_maps, dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, A, (const float*)terms, maps, (const float*)y, (const uint32_t*)ybits, accumulate);
-            hipLaunchKernelGGL((dev::k_giant_replay_maps<P, U>), dim3(A.ngiant), dim3(64), 0, gs, pa, A, y, ybits, accumulate, (const U*)terms, (const dev::gchunk_state*)maps, bounds,
-                               (const int32_t*)L.spec_off);
-            (*launches) += 2;
-          } else
-            hipLaunchKernelGGL((dev::k_spmv_giant<P, T, U, V, E, USE_VP, REDUCE_F32_ADD>), dim3(A.ngiant), dim3(dev::kGiant), 0, gs, pa, A, x, xbits, vp, y,
-                               ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), (const U*)terms, (const unsigned long long*)nullptr, want, (dev::gchunk_state*)nullptr,
-                               bounds, (const int32_t*)L.spec_off);
-          hipLaunchKernelGGL((dev::k_giant_verify_chunks<P, U>), dim3((A.ngchunk + WPB - 1) / WPB), dim3(dev::kBlock), 0, gs, pa, A, (const U*)terms,
-                             (const unsigned long long*)bounds, (const U*)y, redo, L.spec_off);
-          hipLaunchKernelGGL((dev::k_giant_fold_ordered<P, U, V>), dim3((A.ngiant + WPB - 1) / WPB), dim3(dev::kBlock), 0, gs, pa, A, vp, y, ybits,
-                             accumulate, (const U*)terms, (const unsigned long long*)nullptr, want, (const int32_t*)redo, (const int32_t*)L.spec_off);
-          (*launches) += 2;
-          two_pass = true;
-        }
-      }
-      if constexpr (dev::stageable<U>::value && std::is_trivially_copyable<U>::value && (sizeof(U) == 4 || sizeof(U) == 8)) {
-        // any function: associativity on the operands at hand, speculated and proven chunk by chunk
-        void *p6 = nullptr, *p7 = nullptr, *p15 = nullptr;
-        if (!two_pass && may_speculate && gm_graph_workspace(g, 6, (size_t)A.giant_edges * sizeof(U) + 64, &p6) == GM_OK &&
-            (xbits == nullptr || gm_graph_workspace(g, 14, (size_t)A.giant_edges / 8 + 64, &p7) == GM_OK) && gm_graph_workspace(g, 15, o_end, &p15) == GM_OK) {
-          const U* terms = (const U*)p6;
-          const unsigned long long* tpres = (const unsigned long long*)p7;
-          char* w = (char*)p15;
-          U *bval = (U*)w, *tval = (U*)(w + o_tval), *fin = (U*)(w + o_fin);
-          int32_t *redo = (int32_t*)(w + o_redo), *bhas = (int32_t*)(w + o_bhas), *thas = (int32_t*)(w + o_thas), *finhas = (int32_t*)(w + o_finhas);
-          const unsigned cgrid = (unsigned)((A.ngchunk + WPB - 1) / WPB), rgrid = (unsigned)((A.ngiant + WPB - 1) / WPB);
-          GM_HIP_OK(hipMemsetAsync(redo, 0, (size_t)A.ngiant * 4, gs));
-          if (!L.terms_ready) {
-            hipLaunchKernelGGL((dev::k_giant_terms<P, T, U, V, E, USE_VP>), dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, pa, A, x, xbits, vp, (U*)p6,
-                               (unsigned long long*)p7 GM_DBG_ARG(L.opt.debug_flags), (dev::gchunk_state*)nullptr);
-            (*launches)++;
-          }
-          hipLaunchKernelGGL((dev::k_giant_chunk_totals<P, U, V>), dim3(cgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, terms, tpres, tval, thas,
-                             (const int32_t*)L.spec_off);
-          hipLaunchKernelGGL((dev::k_giant_chunk_scan<P, U, V>), dim3(rgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, y, ybits, accumulate, (const U*)tval,
-                             (const int32_t*)thas, bval, bhas, fin, finhas, (const int32_t*)L.spec_off);
-          hipLaunchKernelGGL((dev::k_giant_verify_chunks_any<P, U, V>), dim3(cgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, want, terms, tpres, (const U*)bval,
-                             (const int32_t*)bhas, (const U*)fin, (const int32_t*)finhas, redo, L.spec_off);
-          hipLaunchKernelGGL((dev::k_giant_fold_ordered<P, U, V>), dim3(rgrid), dim3(dev::kBlock), 0, gs, pa, A, vp, y, ybits, accumulate, terms, tpres, want,
-                             (const int32_t*)redo, (const int32_t*)L.spec_off);
-          (*launches) += 3;
-          two_pass = true;
-        }
-      }
-      if constexpr (dev::stageable<U>::value && std::is_trivially_copyable<U>::value) {
-        void *p6 = nullptr, *p7 = nullptr;
-        if (two_pass) {
-        } else
-        if (L.opt.ordered_giant_two_pass != 0 && gm_graph_workspace(g, 6, (size_t)A.giant_edges * sizeof(U) + 64, &p6) == GM_OK &&
-            (xbits == nullptr || gm_graph_workspace(g, 14, (size_t)A.giant_edges / 8 + 64, &p7) == GM_OK)) {
-          if (!L.terms_ready) {
-            hipLaunchKernelGGL((dev::k_giant_terms<P, T, U, V, E, USE_VP>), dim3(A.ngchunk), dim3(dev::kBlock), 0, gs, pa,
-                               A, x, xbits, vp, (U*)p6, (unsigned long long*)p7 GM_DBG_ARG(L.opt.debug_flags), (dev::gchunk_state*)nullptr);
-            (*launches)++;
-          }
-          hipLaunchKernelGGL((dev::k_giant_fold_ordered<P, U, V>), dim3((A.ngiant + WPB - 1) / WPB), dim3(dev::kBlock), 0, gs, pa, A, vp, y,
-                             ybits, accumulate, (const U*)p6, (const unsigned long long*)p7, want);
-          two_pass = true;
-        }
-      }
-      if (!two_pass)
-        hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, REDUCE_ORDERED>),
-                           dim3((A.ngiant + WPB - 1) / WPB), dim3(dev::kBlock), 0, gs, pa, A, A.giant_row, A.ngiant, x,
-                           xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-    }
-    (*launches)++;
+    p.giant_rows(gs);
     if (overlap) {
       if (timer) timer->aux_mark(gs);
       GM_HIP_OK(hipEventRecord(aux->join, gs));
@@ -521,116 +726,12 @@ void launch_spmv_rk(const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& 
       timer->mark(TAG_GIANT);
     }
   }
-  if (A.nblk > 0 && RK == REDUCE_LAST) {
-    // a=b: one lane per row over the whole row range (short rows pick themselves by their length)
-    if constexpr (RK == REDUCE_LAST) {
-      hipLaunchKernelGGL((dev::k_spmv_short_last<P, T, U, V, E, USE_VP>), dim3(grid_for(A.nrows)), dim3(dev::kBlock), 0, s,
-                         pa, A, x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want, xsum);
-      (*launches)++;
-      if (timer) timer->mark(TAG_ROWBLOCK);
-    }
-  } else if (A.nblk > 0) {
-    bool done = false;
-    if constexpr (!USE_VP && sizeof(T) == 4 && sizeof(U) == 4 && RK != REDUCE_LAST && std::is_trivially_copyable<T>::value) {
-      // persistent workgroups sharing a large LDS hot set, row-blocks taken by waves (kernels.hpp: k_spmv_rowwave)
-      const int form = L.opt.rowwave_form & 15;
-      const bool any_size = (L.opt.rowwave_form & 16) != 0;  // (tests: also for small graphs)
-      const bool whole_cols = A.hot_base == 0 && A.hot_len >= A.ncols;  // (not a column tile: the untiled pass of a tiled graph, or an untiled graph)
-      if (form > 0 && xbits == nullptr && want == nullptr && !program_row_filter<P>::enabled && (persistent_forms_pay(A) || any_size) &&
-          !(whole_cols && (keep || L.tiled_untiled_pass) && L.opt.untiled_pass_plain != 0)) {
-        auto persistent = [&](auto block_c, auto hot_c, int fit) {
-          constexpr int BLOCK = decltype(block_c)::value, HOT = decltype(hot_c)::value;
-          const int per_cu = L.opt.persist_per_cu > 0 && L.opt.persist_per_cu < fit ? L.opt.persist_per_cu : fit;
-          int grid = cu_count() * per_cu;
-          const int need = (A.nblk + BLOCK / 64 - 1) / (BLOCK / 64);
-          if (grid > need) grid = need;
-          hipLaunchKernelGGL((dev::k_spmv_rowwave<P, T, U, V, E, BLOCK, HOT>), dim3(grid), dim3(BLOCK), 0, s, pa, A, x, y, ybits, accumulate);
-          done = true;
-        };
-        // (1024 threads / 30720 entries: the row-block time falls by 15 % but the kernels of the auxiliary stream find no
-        // LDS next to it and the iteration gains nothing; 20480 entries leave them room; 512 / 16384 and 256 / 8192: no gain)
-        if (form == 4) persistent(std::integral_constant<int, 1024>(), std::integral_constant<int, 20480>(), 1);
-      }
-    }
-    if (done) {
-    } else if (xbits == nullptr)
-      hipLaunchKernelGGL((dev::k_spmv_rowblock<P, T, U, V, E, USE_VP, true, RK>), dim3(A.nblk), dim3(dev::kBlock), 0, s, pa, A,
-                         x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-    else
-      hipLaunchKernelGGL((dev::k_spmv_rowblock<P, T, U, V, E, USE_VP, false, RK>), dim3(A.nblk), dim3(dev::kBlock), 0, s, pa, A,
-                         x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-    (*launches)++;
+  if (A.nblk > 0) {
+    p.short_rows(keep);
     if (timer) timer->mark(TAG_ROWBLOCK);
   }
   if (A.nmid > 0) {
-    if (grouped && want != nullptr) {  // a row bitmap governs: 64 list entries per wave, only the wanted rows are worked on
-      const int groups = (A.nmid + 63) / 64;
-      // (running this kernel on the auxiliary stream next to the short rows' kernel was measured: both want every wave
-      // slot of the chip, side by side each takes twice as long -- RMAT-26, first bottom-up level: 1.55 against 1.52 ms)
-      bool done = false;
-      if constexpr (RK == REDUCE_LAST) {
-        if (L.opt.last_rows_lanes == 16) {
-          hipLaunchKernelGGL((dev::k_spmv_wave_grouped<P, T, U, V, E, USE_VP, RK, 16>), dim3((groups + WPB - 1) / WPB),
-                             dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits, vp, y, ybits, accumulate
-                             GM_DBG_ARG(L.opt.debug_flags), want, xsum);
-          done = true;
-        }
-      }
-      if (!done)
-        hipLaunchKernelGGL((dev::k_spmv_wave_grouped<P, T, U, V, E, USE_VP, RK>), dim3((groups + WPB - 1) / WPB),
-                           dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits, vp, y, ybits, accumulate
-                           GM_DBG_ARG(L.opt.debug_flags), want, xsum);
-    } else if (wave16_ok<U, USE_VP, RK>() && !(L.opt.debug_flags & dev::DBG_NO_WAVE16)) {
-      if constexpr (wave16_ok<U, USE_VP, RK>()) {
-        // ordered folds: the long rows at the head of the list get a wave each, the rest are folded 16 to a wave
-        const int nlong = A.nmid_long < A.nmid ? A.nmid_long : A.nmid;
-        const int rest = A.nmid - nlong;
-        const int groups = (rest + dev::kWaveRows - 1) / dev::kWaveRows;
-        // the long rows: a wave each (k_spmv_wave), on the auxiliary stream during column-tile passes.  (Handing them to
-        // the waves of the persistent kernel below -- one launch, long rows first off the same work counter -- was
-        // measured at RMAT-26: 6.6 -> 7.9 ms per iteration.  wave_row's ordered fold is a serial chain per wave and wants
-        // the 32 waves per CU the plain kernel gets, not the 16 of a workgroup that holds 90 KB of LDS.)
-        if (nlong > 0) {
-          hipStream_t ls = s;
-          if (long_on_aux) {
-            fork_aux();
-            ls = aux->s;
-            if (timer) timer->aux_mark(ls);
-          }
-          hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, RK>), dim3((nlong + WPB - 1) / WPB), dim3(dev::kBlock), 0, ls,
-                             pa, A, A.mid_row, nlong, x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-          if (long_on_aux) {
-            if (timer) timer->aux_mark(ls);
-            GM_HIP_OK(hipEventRecord(aux->join, ls));  // (re-recorded behind the giant passes' record: the wait below sees this one)
-          }
-        }
-        // Large graphs: the 16-row groups go to persistent 1024-thread workgroups that load the slice's 22528 busiest x
-        // entries into LDS once, their waves taking groups in an interleaved order (kernels.hpp: k_spmv_wave16p; measured
-        // in profiles/r03_persistent_kernels.md)
-        bool done = false;
-        if constexpr (sizeof(T) == 4 && sizeof(U) == 4) {
-          const int form = persistent_forms_pay(A) || (L.opt.wave16_form & 16) ? (L.opt.wave16_form & 15) : 0;
-          if (rest > 0 && form == 2) {
-            constexpr int BLOCK = 1024, HOT = 22528;
-            int grid = cu_count();
-            const int need = (groups + BLOCK / 64 - 1) / (BLOCK / 64);
-            if (grid > need) grid = need;
-            hipLaunchKernelGGL((dev::k_spmv_wave16p<P, T, U, V, E, BLOCK, HOT>), dim3(grid), dim3(BLOCK), 0, s, pa, A, A.mid_row + nlong, rest,
-                               x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-            done = true;
-          }
-        }
-        if (!done && rest > 0) {
-          constexpr int W16 = dev::kWave16Block / 64;
-          hipLaunchKernelGGL((dev::k_spmv_wave16<P, T, U, V, E>), dim3((groups + W16 - 1) / W16), dim3(dev::kWave16Block), 0, s, pa, A,
-                             A.mid_row + nlong, rest, x, xbits, vp, y, ybits, accumulate GM_DBG_ARG(L.opt.debug_flags), want);
-        }
-      }
-    } else
-      hipLaunchKernelGGL((dev::k_spmv_wave<P, T, U, V, E, USE_VP, RK>), dim3((A.nmid + WPB - 1) / WPB),
-                         dim3(dev::kBlock), 0, s, pa, A, A.mid_row, A.nmid, x, xbits, vp, y, ybits, accumulate
-                         GM_DBG_ARG(L.opt.debug_flags), want);
-    (*launches)++;
+    p.wave_rows(long_on_aux, fork_aux);
     if (timer && !long_on_aux) timer->mark(TAG_WAVE);
   }
   if (keep) {
@@ -671,8 +772,7 @@ template <class P, class T, class U, class V, class E>
 void launch_spmv_vp(bool use_vp, const Launch& L, const dev::ProgArg<P>& pa, const gm_csr_t& A, const T* x, const uint32_t* xbits, const V* vp,
                     U* y, uint32_t* ybits, int accumulate, int rk = REDUCE_ORDERED, const uint32_t* want = nullptr, bool grouped = false,
                     const uint32_t* xsum = nullptr) {
-  if (use_vp) launch_spmv<P, T, U, V, E, true>(L, pa, A, x, xbits, vp, y, ybits, accumulate, rk, want, grouped, xsum);
-  else launch_spmv<P, T, U, V, E, false>(L, pa, A, x, xbits, vp, y, ybits, accumulate, rk, want, grouped, xsum);
+  with_flag(use_vp, [&](auto vp_c) { launch_spmv<P, T, U, V, E, decltype(vp_c)::value>(L, pa, A, x, xbits, vp, y, ybits, accumulate, rk, want, grouped, xsum); });
 }
 
 // ---- the iteration loop ---------------------------------------------------------------------------------------------
@@ -737,7 +837,7 @@ class Run {
   bool guess_f32_add = false;  // rk is the ordered fold and reduce_function answers like a float addition: speculation for the giant rows only, proven chunk by chunk
   bool can_push = false, xsparse_ok = false, lazy_send = false;
   bool guided = false;         // an ORDERED fold over a sparse x on a large unsharded graph: levels with small active sets only fold the rows that have an active in-neighbour
-  uint32_t* d_mark = nullptr;  // ... their bitmap (workspace slot 8)
+  uint32_t* d_mark = nullptr;  // ... their bitmap (workspace slot GM_WS_ROW_MARKS)
   const int32_t *dev_of_native = nullptr, *native_of_dev = nullptr;
   xentry_t* d_gather = nullptr;
   unsigned long long* d_best = nullptr;
@@ -745,12 +845,12 @@ class Run {
   int32_t* d_touched = nullptr;
   unsigned int* d_off = nullptr;
   uint32_t* d_want = nullptr;  // row-filter bits (program_row_filter), kept current by k_apply
-  void* flag_v = nullptr;      // 4096 bytes: [2] list counter, [3] touched counter, [4..9] frontier stats, [127] changed flag, [128..] striped stats
+  void* flag_v = nullptr;      // the run's flag / statistics block (FlagBlock)
   int* d_changed = nullptr;
   unsigned int *d_count = nullptr, *d_tcount = nullptr;
   unsigned long long *d_stats = nullptr, *d_striped = nullptr;
-  static constexpr size_t striped_bytes = (size_t)dev::kStatSlots * 4 * sizeof(unsigned long long);
-  int* h_changed = nullptr;  // pinned mirror of flag_v
+  static constexpr size_t striped_bytes = FlagBlock::kStripedBytes;
+  int* h_changed = nullptr;  // pinned mirror of flag_v (same layout)
   unsigned long long *h_stats = nullptr, *h_striped = nullptr;
   int stats_grid = 1;
   bool grouped_waves = true;
@@ -770,7 +870,7 @@ class Run {
   Launch launch_ctx() {
     Launch L{g, s, opt, &st.spmv_launches, &timer, &aux};
     L.guess_f32_add = guess_f32_add;
-    L.spec_off = flag_v ? (int32_t*)flag_v + 720 : nullptr;
+    L.spec_off = flag_v ? FlagBlock::at<int32_t>(flag_v, FlagBlock::kSpecOff) : nullptr;
     return L;
   }
   static void die(const char* what) {
@@ -895,24 +995,22 @@ class Run {
              !(opt.debug_flags & dev::DBG_NO_PUSH) && gm_graph_csr(g, GM_DIR_IN, &Asrc) == GM_OK;
     if (guided) {
       void* pm = nullptr;
-      if (gm_graph_workspace(g, 8, ((size_t)(n + 31) / 32 + 2) * 4, &pm) == GM_OK) d_mark = (uint32_t*)pm; else guided = false;
+      if (gm_graph_workspace(g, GM_WS_ROW_MARKS, ((size_t)(n + 31) / 32 + 2) * 4, &pm) == GM_OK) d_mark = (uint32_t*)pm; else guided = false;
     }
     if (verbose && guided) printf("GraphMat(HIP): guided pull: iterations whose active set owns few out-edges only fold the rows it reaches\n");
 
-    gm_graph_workspace(g, 0, 4096, &flag_v);
-    // (the changed flag sits directly in front of the striped statistics, so that one memset clears and one copy fetches
-    // "flag + statistics": every call the host makes between two short levels of a traversal shows up as idle time on the GPU)
-    d_changed = (int*)flag_v + 127;
-    GM_HIP_OK(hipMemsetAsync((int*)flag_v + 720, 0, 4, s));  // Launch::spec_off
-    d_count = (unsigned int*)flag_v + 2;   // entries of d_list (the active set, when it is small)
-    d_tcount = (unsigned int*)flag_v + 3;  // entries of d_touched (destinations bid for in a top-down step)
-    d_stats = (unsigned long long*)flag_v + 2;    // byte offset 16
-    d_striped = (unsigned long long*)flag_v + 64;  // byte offset 512: kStatSlots x 4 u64 (k_apply)
+    gm_graph_workspace(g, GM_WS_FLAGS, FlagBlock::kBytes, &flag_v);
+    d_changed = FlagBlock::at<int>(flag_v, FlagBlock::kChanged);
+    GM_HIP_OK(hipMemsetAsync(FlagBlock::at<int32_t>(flag_v, FlagBlock::kSpecOff), 0, 4, s));
+    d_count = FlagBlock::at<unsigned int>(flag_v, FlagBlock::kListCount);
+    d_tcount = FlagBlock::at<unsigned int>(flag_v, FlagBlock::kTouchedCount);
+    d_stats = FlagBlock::at<unsigned long long>(flag_v, FlagBlock::kStats);
+    d_striped = FlagBlock::at<unsigned long long>(flag_v, FlagBlock::kStriped);
     void *res_stream = nullptr, *res_fork = nullptr, *res_join = nullptr, *res_pinned = nullptr;
     if (gm_graph_run_resources(g, &res_stream, &res_fork, &res_join, &res_pinned) != GM_OK) die(gm_last_error());
-    h_changed = (int*)res_pinned + 127;  // (the pinned mirror has the layout of flag_v)
-    h_stats = (unsigned long long*)res_pinned;
-    h_striped = (unsigned long long*)res_pinned + 64;
+    h_changed = FlagBlock::at<int>(res_pinned, FlagBlock::kChanged);
+    h_stats = FlagBlock::at<unsigned long long>(res_pinned, FlagBlock::kStats);
+    h_striped = FlagBlock::at<unsigned long long>(res_pinned, FlagBlock::kStriped);
     stats_grid = grid_for(n) < 2048 ? grid_for(n) : 2048;
     const bool xsparse_candidate = xsparse_ok;  // (the same on every shard: program, run mode and exchange capabilities)
     if (xsparse_ok) {
@@ -922,8 +1020,8 @@ class Run {
     }
     if (can_push || xsparse_ok || guided) {
       void *pb = nullptr, *pl = nullptr, *pt = nullptr;
-      if (gm_graph_workspace(g, 7, (size_t)n * 4 + 1024 + ((size_t)dev::kSparseListCap + 64 + dev::kSparseListCap / dev::kBlock + 64) * 4, &pl) != GM_OK ||
-          (can_push && (gm_graph_workspace(g, 6, (size_t)n * 8 + 64, &pb) != GM_OK || gm_graph_workspace(g, 10, (size_t)n * 4 + 1024, &pt) != GM_OK))) {
+      if (gm_graph_workspace(g, GM_WS_ACTIVE_LIST, (size_t)n * 4 + 1024 + ((size_t)dev::kSparseListCap + 64 + dev::kSparseListCap / dev::kBlock + 64) * 4, &pl) != GM_OK ||
+          (can_push && (gm_graph_workspace(g, GM_WS_PUSH_BIDS, (size_t)n * 8 + 64, &pb) != GM_OK || gm_graph_workspace(g, GM_WS_TOUCHED, (size_t)n * 4 + 1024, &pt) != GM_OK))) {
         can_push = false;
         xsparse_ok = false;
         guided = false;
@@ -938,11 +1036,11 @@ class Run {
         GM_HIP_OK(hipMemsetAsync(d_count, 0, 4, s));
         hipLaunchKernelGGL(dev::k_frontier_stats, dim3(stats_grid), dim3(dev::kBlock), 0, s, (const uint32_t*)d_active, Asrc.rowptr, n, d_stats, d_list,
                            d_count);
-        GM_HIP_OK(hipMemcpyAsync(h_stats + 2, d_stats, 24, hipMemcpyDeviceToHost, s));
+        GM_HIP_OK(hipMemcpyAsync(h_stats, d_stats, 24, hipMemcpyDeviceToHost, s));
         GM_HIP_OK(hipStreamSynchronize(s));
-        frontier_v = h_stats[2];
-        frontier_e = h_stats[3];
-        frontier_maxdeg = h_stats[4];
+        frontier_v = h_stats[0];
+        frontier_e = h_stats[1];
+        frontier_maxdeg = h_stats[2];
         list_ready = frontier_v <= (unsigned long long)dev::kSparseListCap;  // listed by the same pass
       }
     }
@@ -966,7 +1064,7 @@ class Run {
     // row-filter bits (program_row_filter): one pass over the vertex properties now, kept current by k_apply
     if constexpr (program_row_filter<P>::enabled) {
       void* pw = nullptr;
-      if (gm_graph_workspace(g, 8, ((size_t)(n + 31) / 32 + 2) * 4, &pw) == GM_OK) {
+      if (gm_graph_workspace(g, GM_WS_ROW_MARKS, ((size_t)(n + 31) / 32 + 2) * 4, &pw) == GM_OK) {
         d_want = (uint32_t*)pw;
         dev::ProgArg<P> pa0 = dev::make_prog_arg(gp);
         // (rows past n_live have no edges: no kernel ever looks at their bit)
@@ -978,18 +1076,29 @@ class Run {
 
   void finish(int it) {
     GM_HIP_OK(hipStreamSynchronize(s));
-    gm_graph_note_set(g, 3, (int64_t)sparse_sweeps);
-    gm_graph_note_set(g, 4, (int64_t)short_folds);
-    gm_graph_note_set(g, 7, (int64_t)fold_applies);
-    gm_graph_note_set(g, 5, (int64_t)((unsigned long long)step_count[STEP_PULL] | (unsigned long long)step_count[STEP_LIST] << 16 |
-                                      (unsigned long long)step_count[STEP_BITS] << 32 | (unsigned long long)step_count[STEP_DENSE_PUSH] << 48));
-    gm_graph_note_set(g, 6, (int64_t)step_kinds);
+    gm_graph_note_set(g, GM_NOTE_SPARSE_SWEEPS, (int64_t)sparse_sweeps);
+    gm_graph_note_set(g, GM_NOTE_SHORT_FOLDS, (int64_t)short_folds);
+    gm_graph_note_set(g, GM_NOTE_FOLD_APPLIES, (int64_t)fold_applies);
+    gm_graph_note_set(g, GM_NOTE_STEP_COUNTS, (int64_t)((unsigned long long)step_count[STEP_PULL] | (unsigned long long)step_count[STEP_LIST] << 16 |
+                                                        (unsigned long long)step_count[STEP_BITS] << 32 | (unsigned long long)step_count[STEP_DENSE_PUSH] << 48));
+    gm_graph_note_set(g, GM_NOTE_STEP_KINDS, (int64_t)step_kinds);
     tick("loop done", it);
     aux.finish();
     st.iterations = it;
     timer.finish(&st);
     gm_graph_record_stats(g, &st);
     tick("teardown done", 0);
+  }
+
+  // the second message buffer of the overlapped schedules: adopted from the caller (callback exchange: the collective library must know
+  // it), or simply the library's own when the exchange is native; null = none
+  T* second_message_buffer() {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ext = 0;
+    bool have = gm_graph_workspace_info(g, GM_WS_X2, &p, &bytes, &ext) == GM_OK && ext && p != nullptr && bytes >= (size_t)desc.ndevice * sizeof(T);
+    if (!have && gm_graph_exchange_is_native(g)) have = gm_graph_workspace(g, GM_WS_X2, (size_t)desc.ndevice * sizeof(T) + 64, &p) == GM_OK && p != nullptr;
+    return have ? (T*)p : nullptr;
   }
 
   // ---- schedule: the overlapped two-stage loop of sharded fixed-count ALL_VERTICES / OUT_EDGES runs ------------------------
@@ -1013,21 +1122,14 @@ class Run {
   }
   // returns the iterations done, or -1 when the shards could not agree on a split (the caller runs the plain loop)
   int run_two_stage() {
-    void* x2v = nullptr;
-    size_t x2_bytes = 0;
-    int x2_ext = 0;
     int32_t rs = 0, bs = 0, ms = 0;
     bool staged = false;
-    // the second message buffer: adopted from the caller (callback exchange: the collective library must know it), or
-    // simply the library's own when the exchange is native
-    bool have_x2 = gm_graph_workspace_info(g, 9, &x2v, &x2_bytes, &x2_ext) == GM_OK && x2_ext && x2v != nullptr && x2_bytes >= (size_t)desc.ndevice * sizeof(T);
-    if (!have_x2 && gm_graph_exchange_is_native(g))
-      have_x2 = gm_graph_workspace(g, 9, (size_t)desc.ndevice * sizeof(T) + 64, &x2v) == GM_OK && x2v != nullptr;
-    if (have_x2) {
+    T* const x2v = second_message_buffer();
+    if (x2v != nullptr) {
       // every shard must use the same split (the parts are the same rows of every slice): take the largest of the shards'
       // own choices, then check that it suits everybody
       int64_t agreed = 0;
-      if (gm_graph_note_get(g, 0, &agreed) == GM_OK) {  // note 0: the split the shards agreed on in an earlier run (0 = none)
+      if (gm_graph_note_get(g, GM_NOTE_TWO_STAGE_SPLIT, &agreed) == GM_OK) {  // the split the shards agreed on in an earlier run (0 = none)
         rs = (int32_t)agreed;
         staged = rs > 0 && gm_graph_split(g, GM_DIR_OUT, opt.two_stage_head_permille, &rs, &bs, &ms) == GM_OK;
       } else {
@@ -1037,13 +1139,13 @@ class Run {
         int fine = (rs >= 64 && rs < n_live && gm_graph_split(g, GM_DIR_OUT, opt.two_stage_head_permille, &rs, &bs, &ms) == GM_OK) ? 1 : 0;
         gm_graph_exchange(g, GM_XCHG_CONVERGED, nullptr, 0, nullptr, &fine);
         staged = fine == 1;
-        gm_graph_note_set(g, 0, staged ? (int64_t)rs : 0);
+        gm_graph_note_set(g, GM_NOTE_TWO_STAGE_SPLIT, staged ? (int64_t)rs : 0);
       }
     }
     if (!staged) return -1;
     if (verbose) printf("GraphMat(HIP): two-stage schedule, head rows [0,%d) tail rows [%d,%d)\n", rs, rs, n_live);
     T* xcur = x;
-    T* xnext = (T*)x2v;
+    T* xnext = x2v;
     gm_csr_t At = Aout, Ah = Aout;
     At.blk_seg += bs; At.nblk -= bs; At.mid_row += ms; At.nmid -= ms; At.ngiant = 0; At.ngchunk = 0;
     At.nmid_long = Aout.nmid_long > ms ? Aout.nmid_long - ms : 0;
@@ -1147,11 +1249,9 @@ class Run {
                            (const unsigned int*)d_tcount, d_active, d_changed, d_striped, d_want, d_list, d_count);
       };
       if (!combined) {
-        if (use_vp) finish_k(std::true_type(), std::false_type()); else finish_k(std::false_type(), std::false_type());
+        with_flag(use_vp, [&](auto vp_c) { finish_k(vp_c, std::false_type()); });
       } else {
-        if constexpr (sizeof(U) == 4 && std::is_trivially_copyable<U>::value) {
-          if (use_vp) finish_k(std::true_type(), std::true_type()); else finish_k(std::false_type(), std::true_type());
-        }
+        if constexpr (sizeof(U) == 4 && std::is_trivially_copyable<U>::value) with_flag(use_vp, [&](auto vp_c) { finish_k(vp_c, std::true_type()); });
       }
     }
     st.spmv_launches += 2;
@@ -1180,14 +1280,11 @@ class Run {
                          (const unsigned int*)d_off, native_of_dev, d_best, (const uint32_t*)d_want, d_touched, d_tcount);
     } else {
       if constexpr (sizeof(U) == 4 && std::is_trivially_copyable<U>::value) {
-        if (use_vp)
-          hipLaunchKernelGGL((dev::k_push_combine<P, T, U, V, E, true>), dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, pa, Asrc,
+        with_flag(use_vp, [&](auto vp_c) {
+          hipLaunchKernelGGL((dev::k_push_combine<P, T, U, V, E, decltype(vp_c)::value>), dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, pa, Asrc,
                              (const int32_t*)d_list, nf, (const unsigned int*)d_off, (const T*)x, (const V*)d_vp, d_best, (const uint32_t*)d_want, d_touched,
                              d_tcount);
-        else
-          hipLaunchKernelGGL((dev::k_push_combine<P, T, U, V, E, false>), dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, pa, Asrc,
-                             (const int32_t*)d_list, nf, (const unsigned int*)d_off, (const T*)x, (const V*)d_vp, d_best, (const uint32_t*)d_want, d_touched,
-                             d_tcount);
+        });
       }
     }
     timer.mark(TAG_WAVE);
@@ -1230,7 +1327,7 @@ class Run {
                     bool dense_x) {
     if (!rk_unverified || (acc_flags & dev::ACC_READ_PREV)) return;
     rk_unverified = false;
-    unsigned int* d_mis = (unsigned int*)flag_v + 700;
+    unsigned int* d_mis = FlagBlock::at<unsigned int>(flag_v, FlagBlock::kProbeMismatch);
     GM_HIP_OK(hipMemsetAsync(d_mis, 0, 4, s));
     const T* xc = xq;
     const uint32_t* xbc = xb;
@@ -1243,12 +1340,11 @@ class Run {
       if (cnt <= 0) return;
       const int grid = (cnt + dev::kBlock / 64 - 1) / (dev::kBlock / 64);
       if constexpr ((int)program_traits<P>::reduce != (int)REDUCE_AUTO) return;  // (declared strategies are never checked)
-      else if (use_vp)
-        hipLaunchKernelGGL((dev::k_check_rows<P, T, U, V, E, true>), dim3(grid), dim3(dev::kBlock), 0, s, pa, A, rows, cnt, stride, xc, xbc, (const V*)d_vp,
-                           (const U*)y, yb, rowfilter, d_mis);
       else
-        hipLaunchKernelGGL((dev::k_check_rows<P, T, U, V, E, false>), dim3(grid), dim3(dev::kBlock), 0, s, pa, A, rows, cnt, stride, xc, xbc, (const V*)d_vp,
-                           (const U*)y, yb, rowfilter, d_mis);
+        with_flag(use_vp, [&](auto vp_c) {
+          hipLaunchKernelGGL((dev::k_check_rows<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid), dim3(dev::kBlock), 0, s, pa, A, rows, cnt, stride, xc, xbc, (const V*)d_vp,
+                             (const U*)y, yb, rowfilter, d_mis);
+        });
     };
     sample(A.giant_row, A.ngiant, 0);
     sample(A.mid_row, A.nmid < 2048 ? A.nmid : 2048, 0);
@@ -1303,15 +1399,15 @@ class Run {
   }
 
   // The rows that still need an apply pass behind a multiply whose fold applied the short rows: presence bits of the rows with in-edges
-  // that are not short (the sweep's and the giant rows).  Made once per graph into workspace slot 18, which nothing else uses: the slot
+  // that are not short (the sweep's and the giant rows).  Made once per graph into workspace slot GM_WS_FOLD_REST_MASK, which nothing else uses: the slot
   // exists exactly when the mask has been written (a graph's sweep structure and presence bits never change).
   const uint32_t* fold_rest_mask(const gm_sweep_t& sw) {
     const size_t need = ((size_t)nwords + 2) * 4;
     void* pm = nullptr;
     size_t have = 0;
     int ext = 0;
-    if (gm_graph_workspace_info(g, 18, &pm, &have, &ext) == GM_OK && pm != nullptr && have >= need) return (const uint32_t*)pm;
-    if (sw.srow == nullptr || sw.nshort_rows <= 0 || Aout.rowbits == nullptr || gm_graph_workspace(g, 18, need, &pm) != GM_OK || pm == nullptr) return nullptr;
+    if (gm_graph_workspace_info(g, GM_WS_FOLD_REST_MASK, &pm, &have, &ext) == GM_OK && pm != nullptr && have >= need) return (const uint32_t*)pm;
+    if (sw.srow == nullptr || sw.nshort_rows <= 0 || Aout.rowbits == nullptr || gm_graph_workspace(g, GM_WS_FOLD_REST_MASK, need, &pm) != GM_OK || pm == nullptr) return nullptr;
     GM_HIP_OK(hipMemsetAsync(pm, 0, need, s));
     GM_HIP_OK(hipMemcpyAsync(pm, Aout.rowbits, (size_t)nwords * 4, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(dev::k_clear_row_bits, dim3(grid_for(sw.nshort_rows)), dim3(dev::kBlock), 0, s, sw.srow, (int)sw.nshort_rows, (uint32_t*)pm);
@@ -1345,7 +1441,7 @@ class Run {
         const bool two_pass = rk == REDUCE_F32_ADD && std::is_same<U, float>::value;
         void* p6 = nullptr;
         if (two_pass && xb == nullptr && Aout.ngiant > 0 && sw.ngiant_edges > 0 && sw.gcol != nullptr && !(opt.sweep_form & 8) &&
-            gm_graph_workspace(g, 6, (size_t)Aout.giant_edges * sizeof(U) + 64, &p6) == GM_OK)
+            gm_graph_workspace(g, GM_WS_GIANT_TERMS, (size_t)Aout.giant_edges * sizeof(U) + 64, &p6) == GM_OK)
           gterms = (U*)p6;
       }
       GM_HIP_OK(hipEventRecord(aux.fork, s));
@@ -1370,15 +1466,11 @@ class Run {
       // (the giant rows' gathers in a kernel of their own instead of inside the sweep: sweep_form bit 4, or the 768-thread form)
       const bool gather_apart = gterms != nullptr && sw.nsub <= 1 && ((opt.sweep_form & 16) != 0 || w12);
       auto giant_gather = [&]() {
-        bool done = false;
-        if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-          if (Aout.vals != nullptr && sw.gval != nullptr) {
-            hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, true>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, sw.gval, sw.gdst, (int64_t)sw.ngiant_edges, xq, gterms);
-            done = true;
-          }
-        }
-        if (!done)
-          hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, false>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, (const uint32_t*)nullptr, sw.gdst, (int64_t)sw.ngiant_edges, xq, gterms);
+        with_edge_values<E>(Aout.vals != nullptr && sw.gval != nullptr, [&](auto hv) {
+          constexpr bool HV = decltype(hv)::value;
+          hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, HV>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, HV ? sw.gval : (const uint32_t*)nullptr, sw.gdst,
+                             (int64_t)sw.ngiant_edges, xq, gterms);
+        });
         st.spmv_launches++;
       };
       bool chain_done = false;
@@ -1400,7 +1492,7 @@ class Run {
       if (sw.nstream > 0 && sw.sinv != nullptr && sw.wrow_stream != nullptr && xb == nullptr && !w12 && !shorts_blocked && !(opt.sweep_form & 128) &&
           sw.bin_cap == GM_STREAM_BIN && (sw.nstream >= (1ll << 25) || (opt.sweep_form & 256))) {
         void* p16 = nullptr;
-        if (gm_graph_workspace(g, 16, (size_t)sw.nstream_slots * sizeof(U) + 256, &p16) == GM_OK) sterms = (U*)p16;
+        if (gm_graph_workspace(g, GM_WS_SHORT_TERMS, (size_t)sw.nstream_slots * sizeof(U) + 256, &p16) == GM_OK) sterms = (U*)p16;
       }
       const int where = sterms != nullptr ? 4 : shorts_blocked ? 3 : (w12 ? 1 : (gterms != nullptr ? 2 : (opt.sweep_form & 3)));  // (3: behind everything, below; 4: folded from the sweep's products)
       if (where == 1) { La.s = aux.s; La.timer = nullptr; }
@@ -1422,79 +1514,31 @@ class Run {
       if (w12 && stage > GM_SWEEP_MAX_STAGE_W12) stage = GM_SWEEP_MAX_STAGE_W12;
       for (int set = 0; set < sw.nsets; set++) {
         U* gt = (set == 0 && !gather_apart) ? gterms : (U*)nullptr;  // (the first launch gathers for the giant rows)
-        bool with_vals = false;
         // (the launch that holds the short rows' stream groups walks the wave ranges that include them and stores their products)
         const uint32_t* st_rows = (sterms != nullptr && set == 0) ? sw.wrow_stream : sw.wrow;
         U* st_terms = (sterms != nullptr && set == 0) ? sterms : (U*)nullptr;
-        if (sw.nsub > 1) {  // a shard's rows: the message vector is made of nsub owners' ranges (kernels.hpp: k_spmv_sell_sharded)
-          if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-            if (Aout.vals != nullptr) {
-              hipLaunchKernelGGL((dev::k_spmv_sell_sharded<P, T, U, V, E, true>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base,
-                                 sw.scol, sw.sval, st_rows, sw.row_of_slot, sw.lcol, sw.lval, sw.lps, sw.lrow_of_slot, sw.gcol, sw.gval, sw.gdst, sw.gslice, gt, xq, y,
-                                 sw.nsub, sw.stride, sw.hot_words, st_terms);
-              with_vals = true;
-            }
+        with_edge_values<E>(Aout.vals != nullptr, [&](auto hv) {
+          constexpr bool HV = decltype(hv)::value;
+          const uint32_t *sval = HV ? sw.sval : nullptr, *lval = HV ? sw.lval : nullptr, *gval = HV ? sw.gval : nullptr;
+          if (sw.nsub > 1) {  // a shard's rows: the message vector is made of nsub owners' ranges (kernels.hpp: k_spmv_sell_sharded)
+            hipLaunchKernelGGL((dev::k_spmv_sell_sharded<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
+                               st_rows, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, sw.nsub, sw.stride, sw.hot_words, st_terms);
+          } else if (xb != nullptr) {  // a sparse message vector: presence tests per entry, y's presence bits OR-ed in (kernels.hpp: k_spmv_sell_sparse)
+            if (verbose && !said_sparse_sweep) { printf("GraphMat(HIP):   sparse message vector through the sweep (k_spmv_sell_sparse)\n"); said_sparse_sweep = true; }
+            if (set == 0) sparse_sweeps++;
+            hipLaunchKernelGGL((dev::k_spmv_sell_sparse<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
+                               sw.wrow, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, xq, xb, y, ybits);
+          } else if (w12) {  // 768-thread workgroups (kernels.hpp: k_spmv_sell_w12)
+            hipLaunchKernelGGL((dev::k_spmv_sell_w12<P, T, U, V, E, HV>), dim3(256), dim3(768), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, sw.wrow,
+                               sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y);
+          } else if (sterms != nullptr && set == 0) {  // the launch that holds the short rows' stream groups stores their products
+            hipLaunchKernelGGL((dev::k_spmv_sell_stream<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
+                               sw.wrow_stream, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, sterms);
+          } else {
+            hipLaunchKernelGGL((dev::k_spmv_sell<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, sw.wrow,
+                               sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y);
           }
-          if (!with_vals)
-            hipLaunchKernelGGL((dev::k_spmv_sell_sharded<P, T, U, V, E, false>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base,
-                               sw.scol, (const uint32_t*)nullptr, st_rows, sw.row_of_slot, sw.lcol, (const uint32_t*)nullptr, sw.lps, sw.lrow_of_slot, sw.gcol,
-                               (const uint32_t*)nullptr, sw.gdst, sw.gslice, gt, xq, y, sw.nsub, sw.stride, sw.hot_words, st_terms);
-          continue;
-        }
-        if (xb != nullptr) {  // a sparse message vector: presence tests per entry, y's presence bits OR-ed in (kernels.hpp: k_spmv_sell_sparse)
-          if (verbose && !said_sparse_sweep) { printf("GraphMat(HIP):   sparse message vector through the sweep (k_spmv_sell_sparse)\n"); said_sparse_sweep = true; }
-          if (set == 0) sparse_sweeps++;
-          if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-            if (Aout.vals != nullptr) {
-              hipLaunchKernelGGL((dev::k_spmv_sell_sparse<P, T, U, V, E, true>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                                 sw.sval, sw.wrow, sw.row_of_slot, sw.lcol, sw.lval, sw.lps, sw.lrow_of_slot, xq, xb, y, ybits);
-              with_vals = true;
-            }
-          }
-          if (!with_vals)
-            hipLaunchKernelGGL((dev::k_spmv_sell_sparse<P, T, U, V, E, false>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                               (const uint32_t*)nullptr, sw.wrow, sw.row_of_slot, sw.lcol, (const uint32_t*)nullptr, sw.lps, sw.lrow_of_slot, xq, xb, y, ybits);
-          continue;
-        }
-        if (w12) {  // 768-thread workgroups (kernels.hpp: k_spmv_sell_w12)
-          if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-            if (Aout.vals != nullptr) {
-              hipLaunchKernelGGL((dev::k_spmv_sell_w12<P, T, U, V, E, true>), dim3(256), dim3(768), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                                 sw.sval, sw.wrow, sw.row_of_slot, sw.lcol, sw.lval, sw.lps, sw.lrow_of_slot, sw.gcol, sw.gval, sw.gdst, sw.gslice, gt, xq, y);
-              with_vals = true;
-            }
-          }
-          if (!with_vals)
-            hipLaunchKernelGGL((dev::k_spmv_sell_w12<P, T, U, V, E, false>), dim3(256), dim3(768), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                               (const uint32_t*)nullptr, sw.wrow, sw.row_of_slot, sw.lcol, (const uint32_t*)nullptr, sw.lps, sw.lrow_of_slot, sw.gcol,
-                               (const uint32_t*)nullptr, sw.gdst, sw.gslice, gt, xq, y);
-          continue;
-        }
-        if (sterms != nullptr && set == 0) {  // the launch that holds the short rows' stream groups stores their products
-          if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-            if (Aout.vals != nullptr) {
-              hipLaunchKernelGGL((dev::k_spmv_sell_stream<P, T, U, V, E, true>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                                 sw.sval, sw.wrow_stream, sw.row_of_slot, sw.lcol, sw.lval, sw.lps, sw.lrow_of_slot, sw.gcol, sw.gval, sw.gdst, sw.gslice, gt, xq, y, sterms);
-              with_vals = true;
-            }
-          }
-          if (!with_vals)
-            hipLaunchKernelGGL((dev::k_spmv_sell_stream<P, T, U, V, E, false>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                               (const uint32_t*)nullptr, sw.wrow_stream, sw.row_of_slot, sw.lcol, (const uint32_t*)nullptr, sw.lps, sw.lrow_of_slot, sw.gcol,
-                               (const uint32_t*)nullptr, sw.gdst, sw.gslice, gt, xq, y, sterms);
-          continue;
-        }
-        if constexpr (sizeof(E) == 4 && std::is_trivially_copyable<E>::value) {
-          if (Aout.vals != nullptr) {
-            hipLaunchKernelGGL((dev::k_spmv_sell<P, T, U, V, E, true>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                               sw.sval, sw.wrow, sw.row_of_slot, sw.lcol, sw.lval, sw.lps, sw.lrow_of_slot, sw.gcol, sw.gval, sw.gdst, sw.gslice, gt, xq, y);
-            with_vals = true;
-          }
-        }
-        if (!with_vals)
-          hipLaunchKernelGGL((dev::k_spmv_sell<P, T, U, V, E, false>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol,
-                             (const uint32_t*)nullptr, sw.wrow, sw.row_of_slot, sw.lcol, (const uint32_t*)nullptr, sw.lps, sw.lrow_of_slot, sw.gcol,
-                             (const uint32_t*)nullptr, sw.gdst, sw.gslice, gt, xq, y);
+        });
       }
       st.spmv_launches += sw.nsets;
       timer.mark(TAG_WAVE);
@@ -1578,28 +1622,25 @@ class Run {
   // returns the iterations done, or -1 when the schedule cannot run here (the caller runs the plain loop)
   int run_swept_sharded(const gm_sweep_t& sw) {
     if constexpr (kSparseT && sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<U>::value) {
-      void* x2v = nullptr;
-      size_t x2_bytes = 0;
-      int x2_ext = 0;
-      bool have_x2 = gm_graph_workspace_info(g, 9, &x2v, &x2_bytes, &x2_ext) == GM_OK && x2_ext && x2v != nullptr && x2_bytes >= (size_t)desc.ndevice * sizeof(T);
-      if (!have_x2 && gm_graph_exchange_is_native(g)) have_x2 = gm_graph_workspace(g, 9, (size_t)desc.ndevice * sizeof(T) + 64, &x2v) == GM_OK && x2v != nullptr;
-      // the shards' blocks of the gather buffer are equally long: the largest giant-row count, agreed once per graph (note 2; 0 = the
+      T* const x2v = second_message_buffer();
+      const bool have_x2 = x2v != nullptr;
+      // the shards' blocks of the gather buffer are equally long: the largest giant-row count, agreed once per graph (note GM_NOTE_GIANT_GATHER_CAP; 0 = the
       // schedule cannot run: no shard has a giant row, or one has no second message buffer)
       int cap = 0;
       int64_t agreed = 0;
-      if (gm_graph_note_get(g, 2, &agreed) == GM_OK) {
+      if (gm_graph_note_get(g, GM_NOTE_GIANT_GATHER_CAP, &agreed) == GM_OK) {
         cap = (int)agreed;
       } else {
         int mine = have_x2 ? -Aout.ngiant : -(1 << 30);  // (MIN over the shards of -count = -(largest count); a shard without the buffer makes it too large)
         gm_graph_exchange(g, GM_XCHG_CONVERGED, nullptr, 0, nullptr, &mine);
         cap = (-mine >= (1 << 30)) ? 0 : (-mine + 63) / 64 * 64;
-        gm_graph_note_set(g, 2, (int64_t)cap);
+        gm_graph_note_set(g, GM_NOTE_GIANT_GATHER_CAP, (int64_t)cap);
       }
       if (cap <= 0 || cap > dev::kSparseListCap) return -1;
       void *pg = nullptr, *pm = nullptr;
       if (gm_graph_workspace(g, GM_WS_GATHER, (size_t)desc.nshards * (size_t)cap * sizeof(xentry_t) + 256, &pg) != GM_OK) pg = nullptr;
       const size_t mwords = (size_t)nwords + 2;
-      if (gm_graph_workspace(g, 8, 2 * mwords * 4, &pm) != GM_OK) pm = nullptr;
+      if (gm_graph_workspace(g, GM_WS_ROW_MARKS, 2 * mwords * 4, &pm) != GM_OK) pm = nullptr;
       {  // (a shard that could not get its buffers takes the others with it: they must issue the same collectives)
         int fine = (pg != nullptr && pm != nullptr) ? 1 : 0;
         gm_graph_exchange(g, GM_XCHG_CONVERGED, nullptr, 0, nullptr, &fine);
@@ -1613,7 +1654,7 @@ class Run {
         hipLaunchKernelGGL(dev::k_split_row_bits, dim3(grid_for(Aout.ngiant)), dim3(dev::kBlock), 0, s, Aout.giant_row, Aout.ngiant, bits_rest, bits_giant);
       if (verbose) printf("GraphMat(HIP): sharded swept schedule: %d giant rows here, blocks of %d entries; the all-gather travels while they fold\n", Aout.ngiant, cap);
       T* xcur = x;
-      T* xnext = (T*)x2v;
+      T* xnext = x2v;
       const int ag = grid_for(n_live) < dev::kApplyMaxBlocks ? grid_for(n_live) : dev::kApplyMaxBlocks;
       int it = 0;
       {
@@ -1671,13 +1712,13 @@ class Run {
   // Can this run's pull multiply of the OUT adjacency take the column-blocked stream of the short rows (graphmat_hip.h: gm_blocked_t;
   // kernels.hpp: k_spmv_blocked)?  The conditions of the sweep; the structure exists only for graphs without skew (edge values: none, or 4 bytes in its entries).
   bool said_blocked = false, said_sparse_sweep = false, said_short_fold = false;
-  int sparse_sweeps = 0;  // multiplies of this run that took a sparse x through the sweep (note 3 of the graph: tests read it)
-  int short_folds = 0;    // multiplies of this run whose short rows were folded from the sweep's products stream (note 4)
+  int sparse_sweeps = 0;  // multiplies of this run that took a sparse x through the sweep (note GM_NOTE_SPARSE_SWEEPS of the graph: tests read it)
+  int short_folds = 0;    // multiplies of this run whose short rows were folded from the sweep's products stream (GM_NOTE_SHORT_FOLDS)
   // fold + apply + send (kernels.hpp: k_short_fold, FUSED): step_pull says before a multiply that today's path would run k_apply_send behind it
   // (fold_apply_want); multiply_out_swept answers whether its fold applied the short rows and sent for them (fold_applied)
   bool fold_apply_want = false, fold_applied = false, said_fold_apply = false;
-  int fold_applies = 0;   // multiplies of this run whose fold also applied and sent (note 7)
-  // which step every iteration of run_loop took (graphmat_hip.h: notes 5 and 6 of the graph: tests compare them with the rule restated on the host)
+  int fold_applies = 0;   // multiplies of this run whose fold also applied and sent (GM_NOTE_FOLD_APPLIES)
+  // which step every iteration of run_loop took (graphmat_hip.h: notes GM_NOTE_STEP_COUNTS and GM_NOTE_STEP_KINDS of the graph: tests compare them with the rule restated on the host)
   enum { STEP_PULL = 0, STEP_LIST = 1, STEP_BITS = 2, STEP_DENSE_PUSH = 3 };
   unsigned int step_count[4] = {0, 0, 0, 0};  // iterations per kind, saturating at 65535
   unsigned long long step_kinds = 0;          // the kinds of the first 32 iterations, two bits each
@@ -1739,14 +1780,9 @@ class Run {
                            bl.row_of, xq, y, bl.step_count, bl.nsteps, window);
       };
       const bool ub4 = (opt.blocked_form & 16) != 0;
-      bool launched = false;
-      if constexpr (kValsOk) {
-        if (Aout.vals != nullptr) {
-          if (ub4) launch(std::true_type(), std::integral_constant<int, 4>()); else launch(std::true_type(), std::integral_constant<int, 2>());
-          launched = true;
-        }
-      }
-      if (!launched) { if (ub4) launch(std::false_type(), std::integral_constant<int, 4>()); else launch(std::false_type(), std::integral_constant<int, 2>()); }
+      with_edge_values<E>(Aout.vals != nullptr, [&](auto vals_c) {
+        if (ub4) launch(vals_c, std::integral_constant<int, 4>()); else launch(vals_c, std::integral_constant<int, 2>());
+      });
     } else {
       (void)pa; (void)bl;
     }
@@ -1827,12 +1863,10 @@ class Run {
     piece_offsets((int)frontier_v);
     hipLaunchKernelGGL(dev::k_push_bid, dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, Asrc, (const int32_t*)d_list, (int)frontier_v,
                        (const unsigned int*)d_off, native_of_dev, d_best, (const uint32_t*)d_want, (int32_t*)nullptr, (unsigned int*)nullptr);
-    if (use_vp)
-      hipLaunchKernelGGL((dev::k_push_resolve<P, T, U, V, E, true>), dim3(grid_for(n_live)), dim3(dev::kBlock), 0, s, pa, Asrc, xq, dev_of_native,
+    with_flag(use_vp, [&](auto vp_c) {
+      hipLaunchKernelGGL((dev::k_push_resolve<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid_for(n_live)), dim3(dev::kBlock), 0, s, pa, Asrc, xq, dev_of_native,
                          (const V*)d_vp, d_best, y, ybits, n_live);  // (only live rows can have been bid for)
-    else
-      hipLaunchKernelGGL((dev::k_push_resolve<P, T, U, V, E, false>), dim3(grid_for(n_live)), dim3(dev::kBlock), 0, s, pa, Asrc, xq, dev_of_native,
-                         (const V*)d_vp, d_best, y, ybits, n_live);
+    });
     st.spmv_launches += 2;
     timer.mark(TAG_WAVE);
   }
@@ -1896,7 +1930,7 @@ class Run {
         void* ps = nullptr;
         const int xwords = (desc.ndevice + 31) / 32;  // x (and its presence bits) cover every shard's rows
         const int nsum = (xwords / 2 + 31) / 32 + 1;
-        if (gm_graph_workspace(g, 11, (size_t)nsum * 4 + 64, &ps) == GM_OK) {
+        if (gm_graph_workspace(g, GM_WS_XSUM, (size_t)nsum * 4 + 64, &ps) == GM_OK) {
           hipLaunchKernelGGL(dev::k_bits_summary, dim3(grid_for(nsum)), dim3(dev::kBlock), 0, s, xb, xwords, (uint32_t*)ps, nsum);
           xsum = (const uint32_t*)ps;
         }

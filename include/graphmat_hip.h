@@ -444,10 +444,10 @@ int gm_rmat_generate(int scale, uint64_t seed, int64_t first_edge, int64_t count
 #define GM_XCHG_MESSAGES 0
 #define GM_XCHG_CONVERGED 1
 /* Overlapped form, used by fixed-count ALL_VERTICES programs when the caller has also adopted a
- * second message buffer (workspace slot 9): the rows are processed in two stages -- first the
+ * second message buffer (workspace slot GM_WS_X2): the rows are processed in two stages -- first the
  * many rows with few edges, then the few busy rows -- and each stage's part of the NEXT
  * iteration's message vector is exchanged while the other stage computes.
- * GM_XCHG_PART: d_ptr = base of the message buffer to fill (slot 1 or slot 9), h_flag[0] = first
+ * GM_XCHG_PART: d_ptr = base of the message buffer to fill (slot GM_WS_X or GM_WS_X2), h_flag[0] = first
  * row of the part inside every shard's slice, h_flag[1] = number of rows; every shard's rows
  * [h_flag[0], h_flag[0]+h_flag[1]) of its slice must reach all shards.  May return before the data
  * has arrived.  GM_XCHG_WAIT: work enqueued afterwards on the library's stream must see all parts.
@@ -467,7 +467,7 @@ int gm_rmat_generate(int scale, uint64_t seed, int64_t first_edge, int64_t count
 #define GM_XCHG_STATE 4
 #define GM_XCHG_GATHER 5
 #define GM_XCAP_SPARSE 1 /* GM_XCHG_STATE and GM_XCHG_GATHER are implemented */
-#define GM_WS_GATHER 12  /* workspace slot of the gather buffer (adopt it when the collective library must know the buffer) */
+/* (GM_WS_GATHER, the gather buffer's workspace slot, is defined with the other slots next to GM_WS_SLOTS below) */
 typedef int (*gm_exchange_fn)(void* ctx, int kind, void* d_ptr, int64_t elt_bytes, uint32_t* d_bits, int* h_flag);
 int gm_graph_set_exchange(gm_graph_t* g, gm_exchange_fn fn, void* ctx);
 int gm_graph_set_exchange_caps(gm_graph_t* g, int caps); /* GM_XCAP_*; gm_graph_set_exchange resets them to 0 */
@@ -532,8 +532,20 @@ int gm_graph_split(const gm_graph_t* g, int direction, int head_permille, int32_
  * message vector through the sweep (3), whose short rows were folded from the sweep's products stream (4),
  * and whose fold also applied its rows and sent their next messages (7: k_short_fold's fused form).
  * Slot 8 is written by gm_run_sgd, gm_run_rmse and gm_run_sgd_bipartite when they choose their kernels: the path the
- * call takes, one of GM_SGD_PATH_* (a call refused for its K, real_bytes or graph leaves the slot as it was). */
+ * call takes, one of GM_SGD_PATH_* (a call refused for its K, real_bytes or graph leaves the slot as it was).
+ * Slots 0 and 2 are agreements between the shards of a graph, made once and kept for later runs: the head / tail row
+ * split of the two-stage schedule (0; value 0 = no split suits every shard) and the entries per shard of the giant
+ * rows' gather blocks in the sharded swept schedule (2; 0 = the schedule cannot run).  Slot 1 is written by
+ * gm_run_sgd_bipartite: bytes this rank received per iteration. */
 #define GM_NOTE_SLOTS 9
+#define GM_NOTE_TWO_STAGE_SPLIT 0
+#define GM_NOTE_SGD_RING_BYTES 1
+#define GM_NOTE_GIANT_GATHER_CAP 2
+#define GM_NOTE_SPARSE_SWEEPS 3
+#define GM_NOTE_SHORT_FOLDS 4
+#define GM_NOTE_STEP_COUNTS 5
+#define GM_NOTE_STEP_KINDS 6
+#define GM_NOTE_FOLD_APPLIES 7
 #define GM_NOTE_SGD_PATH 8
 #define GM_SGD_PATH_ENGINE 0 /* the program went through the common engine (run_graph_program's kernels) */
 #define GM_SGD_PATH_VECTOR 1 /* the dedicated K = 128 fp32 kernels, dot products on the vector units (k_sgd_multiply) */
@@ -583,8 +595,8 @@ int gm_run_rmse(gm_graph_t* g, void* d_latent, int K, int real_bytes, gm_stream_
  * ring pipeline), the last rank broadcasts the complete sums, and every rank applies them to its copy of the items and
  * its own users' sums to its users: per rank and iteration 2 * nitems * (K + 1) * 4 bytes are received instead of
  * nvertices * K * 4, and the bits are those of one GPU.  Vertices must be users (sources only) or items (destinations
- * only).  K = 128 fp32.  With no communicator (or one rank) this is a single-GPU iteration.  gm_graph_note_get(g, 1)
- * afterwards: bytes this rank received per iteration. */
+ * only).  K = 128 fp32.  With no communicator (or one rank) this is a single-GPU iteration.
+ * gm_graph_note_get(g, GM_NOTE_SGD_RING_BYTES) afterwards: bytes this rank received per iteration. */
 int gm_run_sgd_bipartite(gm_graph_t* g, void* d_latent, int K, int real_bytes, const int32_t* d_item_rows, int nitems, int blocks,
                          double lambda, double step, int iterations, int* iters_done, gm_stream_t stream);
 
@@ -701,12 +713,86 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 /* ---- services for the C++ header layer (include/graphmat/engine.hpp) -------------------------
  * Device scratch owned by the graph, grown on demand and reused across runs (the
  * reference allocates x/y per run_graph_program call, GraphMatRuntime.h:110-120).
- * slot in [0, GM_WS_SLOTS). */
+ * slot in [0, GM_WS_SLOTS).  A slot that is too small is freed and allocated again, so within one run a slot has
+ * ONE user: every use has a name below, and uses that share a number say why they never meet.
+ * (n = rows of the shard, nd = gm_graph_desc_t.ndevice, words(k) = ((k + 31) / 32 + 2) * 4 bytes; T / U = message /
+ * reduction type.  "adopt" = a caller may hand the buffer over with gm_graph_adopt_workspace: the buffers a
+ * collective library has to know.)
+ *
+ *  slot name                 holds                                  bytes                              asked for by                          adopt
+ *   0   GM_WS_FLAGS          the run's flag / statistics block      4096                               engine.hpp Run::setup (FlagBlock),    no
+ *                            (engine.hpp: FlagBlock)                                                   Graph.h, gm_graph.hip (warm-up)
+ *   1   GM_WS_X              message values x                       nd * sizeof(T) + 16                run_graph_program, gm_run_fixed.hpp,  yes
+ *                                                                   (SGD / LDA: nd * K * real + 64)    gm_programs.hip, gm_lda.hip
+ *   2   GM_WS_XBITS          presence words of x                    words(nd)                          the same                              yes
+ *   3   GM_WS_Y              reduced values y                       n * sizeof(U) + 16                 the same                              no
+ *                                                                   (SGD / LDA: n * K * real + 64)
+ *   4   GM_WS_YBITS          presence words of y (the item ring:    words(n)  (ring: 2 * words + 64)   the same                              no
+ *                            received / applied bits)
+ *   5   GM_WS_ALL_ACTIVE     all-active bitmap of a fixed-menu run  words(n)                           gm_run_fixed.hpp                      no
+ *   6   GM_WS_GIANT_TERMS    products stream of the giant rows      giant_edges * sizeof(U) + 64       engine.hpp giant_rows_* and           no
+ *                                                                                                      Run::multiply_out_swept
+ *   6   GM_WS_PUSH_BIDS      bid per destination of top-down steps  n * 8 + 64                         engine.hpp Run::setup (can_push)      no
+ *   6   GM_WS_SGD_ITEM_SUMS  packed item sums + flags of the ring   nitems * (K + 1) * 4 + 256         gm_programs.hip gm_run_sgd_bipartite  no
+ *   7   GM_WS_ACTIVE_LIST    active-set list, then piece offsets    n * 4 + 1024 + (kSparseListCap +   engine.hpp Run::setup (can_push,      no
+ *                            and per-workgroup bases                64 + kSparseListCap / kBlock +     sparse exchange, guided pull)
+ *                                                                   64) * 4
+ *   8   GM_WS_ROW_MARKS      one row bitmap per run: rows reached   words(n)  (swept schedule: twice)  engine.hpp Run::setup,                no
+ *                            by the active set (guided pull), or                                       Run::run_swept_sharded
+ *                            the program's row filter, or the
+ *                            sharded swept schedule's split
+ *                            "rest / giant" row bits
+ *   9   GM_WS_X2             second message buffer                  nd * sizeof(T) + 64                engine.hpp run_two_stage,             yes
+ *                                                                                                      run_swept_sharded
+ *  10   GM_WS_TOUCHED        destinations first bid for in a step   n * 4 + 1024                       engine.hpp Run::setup (can_push)      no
+ *  11   GM_WS_XSUM           64:1 summary of x's presence words     ((nd / 64 + 31) / 32 + 1) * 4 + 64 engine.hpp Run::step_pull             no
+ *  12   GM_WS_GATHER         (device id, message) gather blocks     nshards * cap * entry + 256        engine.hpp Run::setup,                yes
+ *                            of GM_XCHG_GATHER                                                         run_swept_sharded
+ *  13   GM_WS_VPROP_STAGE    vertex properties on their way between nd * sizeof(V) + 64                Graph.h                               no
+ *                            host and device order
+ *  14   GM_WS_GIANT_TPRES    presence bits of the giant rows'       giant_edges / 8 + 64               engine.hpp giant_rows_*               no
+ *                            products (sparse x)
+ *  15   GM_WS_SPECULATION    records of the speculated giant rows   engine.hpp: spec_layout().bytes    engine.hpp giant_rows_*               no
+ *  16   GM_WS_SHORT_TERMS    products stream of the short rows      nstream_slots * sizeof(U) + 256    engine.hpp Run::multiply_out_swept    no
+ *  17   GM_WS_LDA_SUMS       LDA partial sums                       (nchunks + 1) * 20 * 8 + 64        gm_lda.hip                            no
+ *  18   GM_WS_FOLD_REST_MASK rows a fused fold leaves to apply;     words(n)                           engine.hpp Run::fold_rest_mask        no
+ *                            written once per graph: the slot
+ *                            exists exactly when it is valid
+ *  19   free
+ *
+ * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
+ * exact commutative ones of 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
+ * one wave per row (larger ones, which no products stream can hold) and never ask for GM_WS_GIANT_TERMS: that is the
+ * float sums' and the ordered folds' stream.  A run whose probed a=b / commutative strategy fails its cross-check falls
+ * back to the ordered fold, and with the same step gives up top-down steps for good.  gm_run_sgd_bipartite
+ * (GM_WS_SGD_ITEM_SUMS) multiplies with kernels of its own, not with the engine's giant-row passes.
+ * Slot 8: the guided pull is refused to programs with a row filter, and the swept schedule to both. */
 #define GM_WS_SLOTS 20
+#define GM_WS_FLAGS 0
+#define GM_WS_X 1
+#define GM_WS_XBITS 2
+#define GM_WS_Y 3
+#define GM_WS_YBITS 4
+#define GM_WS_ALL_ACTIVE 5
+#define GM_WS_GIANT_TERMS 6
+#define GM_WS_PUSH_BIDS 6
+#define GM_WS_SGD_ITEM_SUMS 6
+#define GM_WS_ACTIVE_LIST 7
+#define GM_WS_ROW_MARKS 8
+#define GM_WS_X2 9
+#define GM_WS_TOUCHED 10
+#define GM_WS_XSUM 11
+#define GM_WS_GATHER 12
+#define GM_WS_VPROP_STAGE 13
+#define GM_WS_GIANT_TPRES 14
+#define GM_WS_SPECULATION 15
+#define GM_WS_SHORT_TERMS 16
+#define GM_WS_LDA_SUMS 17
+#define GM_WS_FOLD_REST_MASK 18
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
- * library): slot 1 = message values x (nvertices * elt bytes), slot 2 = x presence bits
- * ((nvertices+31)/32+2 words).  The library uses the buffer while it is large enough and never
+ * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
+ * ((nvertices+31)/32+2 words); the table above says which other slots a caller may adopt.  The library uses the buffer while it is large enough and never
  * frees it.  d_ptr = NULL returns the slot to library ownership. */
 int gm_graph_adopt_workspace(gm_graph_t* g, int slot, void* d_ptr, size_t bytes);
 /* Per-graph run resources, created once with the graph and destroyed with it: an auxiliary

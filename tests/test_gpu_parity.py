@@ -109,12 +109,12 @@ def test_csr_build_order(env, threads, layout):
 
 
 def _giant_rows_folded_again(api, g):
-    """White box: the engine keeps, in workspace slot 15 of the graph, [ngchunk + 2] chunk boundaries of 8 bytes and then one flag per giant row that
+    """White box: the engine keeps, in workspace slot GM_WS_SPECULATION of the graph, [ngchunk + 2] chunk boundaries of 8 bytes and then one flag per giant row that
     k_giant_verify_chunks* sets when a chunk of the row fails its proof (engine.hpp: multiply_out).  (rows folded again, giant rows), or None."""
     import ctypes as C
     ca = g.csr(api.GM_DIR_OUT)
     ptr, size, ext = C.c_void_p(), C.c_size_t(), C.c_int()
-    if api._lib.lib().gm_graph_workspace_info(g.h, 15, C.byref(ptr), C.byref(size), C.byref(ext)) != 0 or not ptr.value:
+    if api._lib.lib().gm_graph_workspace_info(g.h, api._lib.GM_WS_SPECULATION, C.byref(ptr), C.byref(size), C.byref(ext)) != 0 or not ptr.value:
         return None
     if size.value < (ca.ngchunk + 2) * 8 + ca.ngiant * 4:
         return None
@@ -288,9 +288,11 @@ def test_bfs_depths_closed_form(env, n):
 
 
 # ---------------- the exact fp32 replay on long rows ---------------------------------------------
-def _pagerank_custom(api, ob, nv, s, d, pr0, deg, alpha, iters, threads=1, col_tiles=1):
+def _pagerank_custom(api, ob, nv, s, d, pr0, deg, alpha, iters, threads=1, col_tiles=1, graph_out=None):
     import torch
     g = api.Graph(nv, s, d, np.ones(len(s), np.int32), ref_threads=threads, col_tiles=col_tiles)
+    if graph_out is not None:
+        graph_out.append(g)  # (the caller looks at the graph's structure and scratch afterwards)
     st = torch.zeros((nv, 2), dtype=torch.int32, device=g.device)
     st[:, 0] = g.to_device_order(f32bits(pr0).view(np.int32))
     st[:, 1] = g.to_device_order(np.asarray(deg, np.int32))
@@ -330,6 +332,42 @@ def test_long_row_float_sum_is_bit_exact(env, kind):
     a, b, o = _pagerank_custom(api, ob, nv, src, dst, pr0, deg, 0.0, 1)
     assert (f32bits(a) == f32bits(o)).all(), "exact replay differs from the oracle"
     assert (f32bits(b) == f32bits(o)).all(), "serial long-row fold differs from the oracle"
+
+
+@pytest.mark.parametrize("two_pass,maps", [(0, 1), (1, 1), (2, 1), (2, 0)])
+def test_giant_row_strategies_against_the_oracle(env, two_pass, maps):
+    """Every strategy the engine has for giant rows (engine.hpp: giant_rows), chosen by the options ordered_giant_two_pass (0: one wave per
+    row gathers and folds, 1: products stream + ordered fold, 2: speculated and proven) and giant_maps (the float sum's replay with piece
+    maps, or one workgroup per row), on the star graph of test_long_row_float_sum_is_bit_exact: ~28 000 in-edges per hub, i.e. 7 pieces and
+    more than 3 chunks of 8192 products per row, so every pass has several pieces and several chunks per row.  alpha = 0 makes pagerank := the
+    fp32 row sum; both the declared float sum and the forced ordered fold must give the oracle's bits, and where the speculation runs on
+    values of one sign every chunk must be proven."""
+    api, ob = env
+    L = api._lib.lib()
+    rng = np.random.default_rng(42)
+    nv = 40000
+    hubs = np.array([1, 2, 3, 777, 40000])
+    src = np.repeat(np.arange(1, nv + 1), len(hubs)).astype(np.int32)
+    dst = np.tile(hubs, nv).astype(np.int32)
+    keep = rng.random(len(src)) < 0.7
+    src, dst = src[keep], dst[keep]
+    values = {"wide": (rng.random(nv).astype(np.float32) * np.float32(2.0) ** rng.integers(-20, 10, nv)).astype(np.float32),
+              "mixed_sign": rng.standard_normal(nv).astype(np.float32)}
+    deg = np.ones(nv, np.int32)
+    try:
+        api._lib.check(L.gm_set_option(b"ordered_giant_two_pass", two_pass))
+        api._lib.check(L.gm_set_option(b"giant_maps", maps))
+        for kind, pr0 in values.items():
+            graphs = []
+            a, b, o = _pagerank_custom(api, ob, nv, src, dst, pr0, deg, 0.0, 2, graph_out=graphs)
+            ca = graphs[0].csr(api.GM_DIR_OUT)
+            assert ca.ngiant == 5 and ca.ngchunk > 2 * ca.ngiant, (ca.ngiant, ca.ngchunk)
+            assert (f32bits(a) == f32bits(o)).all(), "declared float sum differs from the oracle (%s)" % kind
+            assert (f32bits(b) == f32bits(o)).all(), "forced ordered fold differs from the oracle (%s)" % kind
+            if two_pass == 2 and kind == "wide":  # (the last run of the helper is the forced ordered fold: speculated, every chunk proven)
+                assert _giant_rows_folded_again(api, graphs[0]) == (0, ca.ngiant)
+    finally:
+        api._lib.check(L.gm_reset_options())
 
 
 @pytest.mark.parametrize("kind,tiles", [("uniform", 1), ("ties", 1), ("growing", 1), ("uniform", 3), ("ties", 4)])

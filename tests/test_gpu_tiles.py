@@ -519,13 +519,13 @@ def test_short_rows_ride_the_sweep(env, scale, tiles, threads, keep, acc_rows):
         n4 = C.c_int64(-1)
         pr, _, it = g.pagerank(7)
         assert it == oit == 7 and (f32bits(pr) == f32bits(opr)).all()
-        assert L.gm_graph_note_get(g.h, 4, C.byref(n4)) == 0 and n4.value == 7
+        assert L.gm_graph_note_get(g.h, api._lib.GM_NOTE_SHORT_FOLDS, C.byref(n4)) == 0 and n4.value == 7
         api._lib.check(L.gm_set_option(b"sweep_form", 128))  # the row-block kernel for the short rows
         pr2, _, _ = g.pagerank(7)
-        assert (f32bits(pr2) == f32bits(opr)).all() and L.gm_graph_note_get(g.h, 4, C.byref(n4)) == 0 and n4.value == 0
+        assert (f32bits(pr2) == f32bits(opr)).all() and L.gm_graph_note_get(g.h, api._lib.GM_NOTE_SHORT_FOLDS, C.byref(n4)) == 0 and n4.value == 0
         api._lib.check(L.gm_set_option(b"sweep_form", 0))  # (a small graph without bit 8: the row-block kernel too)
         pr2, _, _ = g.pagerank(7)
-        assert (f32bits(pr2) == f32bits(opr)).all() and L.gm_graph_note_get(g.h, 4, C.byref(n4)) == 0 and n4.value == 0
+        assert (f32bits(pr2) == f32bits(opr)).all() and L.gm_graph_note_get(g.h, api._lib.GM_NOTE_SHORT_FOLDS, C.byref(n4)) == 0 and n4.value == 0
         api._lib.check(L.gm_set_option(b"sweep_form", 256))
         pru, itu, _ = og.pagerank(-1)
         pr3, _, it3 = g.pagerank(-1)  # (until convergence: ACTIVE_ONLY-free program, but the iteration count must agree too)
@@ -568,13 +568,13 @@ def test_sparse_message_vector_through_the_sweep(env, scale, tiles, threads):
             od, oit = og.sssp(src)
             dist, it = g.sssp(src)
             n3 = C.c_int64(0)
-            assert L.gm_graph_note_get(g.h, 3, C.byref(n3)) == 0
+            assert L.gm_graph_note_get(g.h, api._lib.GM_NOTE_SPARSE_SWEEPS, C.byref(n3)) == 0
             taken += n3.value
             assert it == oit and (dist == od).all(), "source %d" % src
             api._lib.check(L.gm_set_option(b"sweep_form", 32))
             dist2, it2 = g.sssp(src)
             api._lib.check(L.gm_set_option(b"sweep_form", 64))
-            assert L.gm_graph_note_get(g.h, 3, C.byref(n3)) == 0 and n3.value == 0
+            assert L.gm_graph_note_get(g.h, api._lib.GM_NOTE_SPARSE_SWEEPS, C.byref(n3)) == 0 and n3.value == 0
             assert it2 == oit and (dist2 == od).all()
         assert taken >= 3
         g.close()

@@ -141,12 +141,12 @@ def main():
         if sw.nstream <= 0:
             if sw.nedges > 0:
                 fail("no stream groups although the shard has medium rows (%s)" % tag)
-        elif not sw.wrow_stream or L.gm_graph_note_get(g.h, 4, C.byref(n4)) != 0 or n4.value != 6:
+        elif not sw.wrow_stream or L.gm_graph_note_get(g.h, _lib.GM_NOTE_SHORT_FOLDS, C.byref(n4)) != 0 or n4.value != 6:
             fail("the shard's short rows did not go through the sweep (%s): nstream %d, note 4 = %d" % (tag, sw.nstream, n4.value))
         _lib.check(L.gm_set_option(b"sweep_form", form | 128))
         pr_r, _, _ = g.pagerank(6)
         _lib.check(L.gm_set_option(b"sweep_form", form | 256))
-        if L.gm_graph_note_get(g.h, 4, C.byref(n4)) != 0 or n4.value != 0 or not (pr_r.view(np.uint32) == opr.view(np.uint32)).all():
+        if L.gm_graph_note_get(g.h, _lib.GM_NOTE_SHORT_FOLDS, C.byref(n4)) != 0 or n4.value != 0 or not (pr_r.view(np.uint32) == opr.view(np.uint32)).all():
             fail("the row-block kernel for the shard's short rows differs or was not taken (%s)" % tag)
         # ... and the plain loop (all-gather between send and multiply) through the same sweep
         p1 = parts_of(g)

@@ -52,7 +52,7 @@ def main():
             dev = torch.device("cuda", 0)
             bufs = [torch.zeros(g.ndevice * 4 + 64, dtype=torch.uint8, device=dev), torch.zeros((g.ndevice + 31) // 32 + 2, dtype=torch.int32, device=dev),
                     torch.zeros(g.ndevice * 4 + 64, dtype=torch.uint8, device=dev)]
-            for slot, b in zip((1, 2, 9), bufs):
+            for slot, b in zip((_lib.GM_WS_X, _lib.GM_WS_XBITS, _lib.GM_WS_X2), bufs):
                 _lib.check(L.gm_graph_adopt_workspace(g.h, slot, b.data_ptr(), b.numel() * b.element_size()))
             calls = [0]
 
