@@ -315,6 +315,16 @@ class Graph:
         check(self.L.gm_run_lda_loglik(self.h, st.data_ptr(), 20, eta, nterms, C.byref(out), _stream()))
         return out.value, self.to_vertex_order(st)[:, 21].cpu().numpy()
 
+    # ---- triangle counting -------------------------------------------------------------------
+    def triangle_count(self):
+        """gm_run_triangle_count: (total, triangles int64[nv] in vertex order).  triangles[v] = sum over the edges u -> v of the
+        multiset intersection of out(u) and out(v); duplicates and self-loops count as given.  On an upper-triangular input
+        (src < dst, no duplicates) the total is the graph's triangle count."""
+        t = torch.zeros(self.rows, dtype=torch.int64, device=self.device)
+        total = C.c_uint64(0)
+        check(self.L.gm_run_triangle_count(self.h, t.data_ptr(), C.byref(total), _stream()))
+        return int(total.value), self.to_vertex_order(t).cpu().numpy()
+
 
 _hip = None
 

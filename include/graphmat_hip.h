@@ -622,6 +622,15 @@ int gm_run_lda(gm_graph_t* g, gm_lda20_t* d_vp, int K, double alpha, double eta,
 int gm_run_lda_loglik(gm_graph_t* g, gm_lda20_t* d_vp, int K, double eta, int nterms, double* h_total, gm_stream_t stream);
 int gm_lda_edge_init(int edge_value, int K, double* h_out);
 
+/* Triangle counting (what src/TriangleCounting.cpp of the reference computes): out(v) = the sorted multiset of the destinations of
+ * v's edges, c(u, v) = sum over x of min(multiplicity of x in out(u), in out(v)) -- what a two-pointer merge counts.  Duplicate
+ * edges and self-loops are kept as given; on an upper-triangular input (src < dst, no duplicates) the total is the graph's
+ * triangle count.  Whole (unsharded) graphs with both directions; edge values and column tiles are ignored.  Option "tc_form"
+ * chooses between the two count kernels (results do not depend on it). */
+/* triangles[v] = sum over edges u -> v of c(u, v) (the multiset intersection above); d_triangles: [nrows] device order,
+ * overwritten; *h_total (may be NULL) = their sum; returns after the stream has finished when h_total is given */
+int gm_run_triangle_count(gm_graph_t* g, int64_t* d_triangles, uint64_t* h_total, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -629,7 +638,9 @@ int gm_lda_edge_init(int edge_value, int K, double* h_out);
  * (1: column tiles serve equally many gathers, the default; 0: they hold equally many vertices with edges); "sgd_mfma"
  * (0/1: the dot products of K = 128 fp32 SGD on the matrix cores: an opt-in measurement form whose results deviate from the vector
  * form's -- the reference's -- bits by up to ~1e-5 of the vectors' scale, outside the 1e-6 bar; slower as well);
- * "lda_tile" (16 / 32 / 64: edges per step of the dedicated LDA multiply kernel, a measurement knob; results do not depend on it).
+ * "lda_tile" (16 / 32 / 64: edges per step of the dedicated LDA multiply kernel, a measurement knob; results do not depend on it);
+ * "tc_form" (triangle counting, a measurement knob as well: 0 = rows are dealt to the two count kernels automatically, the default;
+ * 1 = every row whose own list fits a wave's LDS share goes to the row kernel; 2 = every row goes to the pieces kernel).
  * Every field of gm_engine_options_t below is also a key: gm_set_option then sets the PROCESS default, which a graph
  * uses unless gm_graph_set_option gave it a value of its own; the environment variable GRAPHMAT_OPTIONS="key=value,..."
  * sets such defaults for applications that cannot call this themselves (the reference's unchanged sources). */
@@ -758,7 +769,15 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *  18   GM_WS_FOLD_REST_MASK rows a fused fold leaves to apply;     words(n)                           engine.hpp Run::fold_rest_mask        no
  *                            written once per graph: the slot
  *                            exists exactly when it is valid
- *  19   free
+ *  19   GM_WS_TC_KEYS        triangle counting: the IN adjacency's  nnz * 4 + 64, with duplicate edges  gm_triangles.hip                      no
+ *                            columns as sort keys (32-bit native    nnz * 12 + 128
+ *                            ids, then the 64-bit (id, occurrence)
+ *                            pairs of a graph with duplicate edges)
+ *  20   GM_WS_TC_PLAN        triangle counting: a class byte per    n + 128 + (n + nnz / 64 + 1) * 12  gm_triangles.hip                      no
+ *                            row, then the pieces' first edges and
+ *                            rows
+ *  21   GM_WS_TC_FLAG        triangle counting: duplicate flag,     64                                 gm_triangles.hip                      no
+ *                            number of pieces, the total
  *
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
  * exact commutative ones of 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
@@ -767,7 +786,7 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  * back to the ordered fold, and with the same step gives up top-down steps for good.  gm_run_sgd_bipartite
  * (GM_WS_SGD_ITEM_SUMS) multiplies with kernels of its own, not with the engine's giant-row passes.
  * Slot 8: the guided pull is refused to programs with a row filter, and the swept schedule to both. */
-#define GM_WS_SLOTS 20
+#define GM_WS_SLOTS 22
 #define GM_WS_FLAGS 0
 #define GM_WS_X 1
 #define GM_WS_XBITS 2
@@ -789,6 +808,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_SHORT_TERMS 16
 #define GM_WS_LDA_SUMS 17
 #define GM_WS_FOLD_REST_MASK 18
+#define GM_WS_TC_KEYS 19
+#define GM_WS_TC_PLAN 20
+#define GM_WS_TC_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
