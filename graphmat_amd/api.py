@@ -325,6 +325,16 @@ class Graph:
         check(self.L.gm_run_triangle_count(self.h, t.data_ptr(), C.byref(total), _stream()))
         return int(total.value), self.to_vertex_order(t).cpu().numpy()
 
+    # ---- connected components ----------------------------------------------------------------
+    def connected_components(self):
+        """gm_run_connected_components: (ncomponents, labels int32[nv] in vertex order, index v-1).  labels[v-1] = the smallest
+        vertex id of v's weakly connected component (directions, duplicates and self-loops ignored); a vertex without
+        edges is its own component."""
+        t = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        n = C.c_int32(0)
+        check(self.L.gm_run_connected_components(self.h, t.data_ptr(), C.byref(n), _stream()))
+        return int(n.value), self.to_vertex_order(t).cpu().numpy()
+
 
 _hip = None
 

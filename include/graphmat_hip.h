@@ -631,6 +631,18 @@ int gm_lda_edge_init(int edge_value, int K, double* h_out);
  * overwritten; *h_total (may be NULL) = their sum; returns after the stream has finished when h_total is given */
 int gm_run_triangle_count(gm_graph_t* g, int64_t* d_triangles, uint64_t* h_total, gm_stream_t stream);
 
+/* Connected components by rounds of min-hooking and pointer jumping (gm_components.hip): a forest of parents over device ids, one
+ * pass over ONE adjacency per round (GM_DIR_OUT when the graph has it, else GM_DIR_IN: a graph built with one direction is
+ * served, and every build gives the same labels), a handful of rounds whatever the diameter.  Whole (unsharded) graphs; edge
+ * values and column tiles are ignored.  gm_graph_last_stats afterwards: iterations = passes over the edges, the last one that
+ * found nothing to do included; send_ms = set-up, spmv_ms = the rounds, apply_ms = labels and count. */
+/* Weakly connected components: edge directions, duplicate edges and self-loops are ignored.
+ * labels[v] = the smallest 1-based VERTEX id (the ids of the .mtx file) in v's component, which is exactly
+ * what apps/label_propagation.cpp prints.  A vertex without edges is its own component.
+ * d_labels: int32 [nrows] in device order, overwritten; unused device slots (native_of_dev == -1) get 0.
+ * *h_ncomponents (may be NULL) = the number of components.  The call returns after the stream has finished. */
+int gm_run_connected_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncomponents, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -778,7 +790,16 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *                            rows
  *  21   GM_WS_TC_FLAG        triangle counting: duplicate flag,     64                                 gm_triangles.hip                      no
  *                            number of pieces, the total
+ *  19   GM_WS_CC_EDGE_ROWS   connected components: the row of       nnz * 4 + 64                       gm_components.hip                     no
+ *                            every edge of the adjacency in use
+ *  20   GM_WS_CC_MIN         connected components: the smallest     n * 4 + 64                         gm_components.hip                     no
+ *                            vertex id per root
+ *  21   GM_WS_CC_FLAG        connected components: the last round   64                                 gm_components.hip                     no
+ *                            that found work, the component count
  *
+ * Slots 19-21: gm_run_triangle_count and gm_run_connected_components are separate calls, neither runs inside the other, and
+ * neither keeps anything in these slots from one call to the next (each writes everything it reads there, every call), so
+ * their uses never live in one run; like all runs on one graph, the calls follow each other on one stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
  * exact commutative ones of 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
  * one wave per row (larger ones, which no products stream can hold) and never ask for GM_WS_GIANT_TERMS: that is the
@@ -811,6 +832,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_TC_KEYS 19
 #define GM_WS_TC_PLAN 20
 #define GM_WS_TC_FLAG 21
+#define GM_WS_CC_EDGE_ROWS 19
+#define GM_WS_CC_MIN 20
+#define GM_WS_CC_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
