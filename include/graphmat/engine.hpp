@@ -964,11 +964,11 @@ class Run {
     if (verbose) printf("GraphMat(HIP): reduce strategy %d (0 ordered, 1 commutative, 2 last, 3 float add)\n", rk);
     // Top-down steps for small active sets (kernels.hpp: k_push_*): REDUCE_LAST programs over OUT_EDGES, running until
     // convergence (the host already syncs once per iteration), unsharded, when the by-source adjacency is available;
-    // REDUCE_COMMUTATIVE programs with a 4-byte reduction type take the list-based steps too, folding with
+    // REDUCE_COMMUTATIVE programs with a reduction type of at most 4 bytes take the list-based steps too, folding with
     // compare-and-swap (k_push_combine).  (A frontier-guided pull for the other reduction kinds -- mark the rows that
     // have an active in-neighbour, multiply only those -- was tried and dropped: on RMAT graphs an active set of any size
     // reaches most busy rows, and the extra passes plus the per-iteration statistics made SSSP 7.0 -> 13 ms on RMAT-22.)
-    const bool comm_push = rk == REDUCE_COMMUTATIVE && sizeof(U) == 4 && std::is_trivially_copyable<U>::value;
+    const bool comm_push = rk == REDUCE_COMMUTATIVE && sizeof(U) <= 4 && std::is_trivially_copyable<U>::value;
     can_push = (rk == REDUCE_LAST || comm_push) && order == OUT_EDGES && act == ACTIVE_ONLY && iterations <= 0 && !multi &&
                !(opt.debug_flags & dev::DBG_NO_PUSH) && gm_graph_csr(g, GM_DIR_IN, &Asrc) == GM_OK && desc.row_lo == 0 && desc.row_hi == desc.ndevice;
     if (can_push) gm_graph_maps(g, &dev_of_native, &native_of_dev);
@@ -1251,7 +1251,7 @@ class Run {
       if (!combined) {
         with_flag(use_vp, [&](auto vp_c) { finish_k(vp_c, std::false_type()); });
       } else {
-        if constexpr (sizeof(U) == 4 && std::is_trivially_copyable<U>::value) with_flag(use_vp, [&](auto vp_c) { finish_k(vp_c, std::true_type()); });
+        if constexpr (sizeof(U) <= 4 && std::is_trivially_copyable<U>::value) with_flag(use_vp, [&](auto vp_c) { finish_k(vp_c, std::true_type()); });
       }
     }
     st.spmv_launches += 2;
@@ -1279,7 +1279,7 @@ class Run {
       hipLaunchKernelGGL(dev::k_push_bid, dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, Asrc, (const int32_t*)d_list, nf,
                          (const unsigned int*)d_off, native_of_dev, d_best, (const uint32_t*)d_want, d_touched, d_tcount);
     } else {
-      if constexpr (sizeof(U) == 4 && std::is_trivially_copyable<U>::value) {
+      if constexpr (sizeof(U) <= 4 && std::is_trivially_copyable<U>::value) {
         with_flag(use_vp, [&](auto vp_c) {
           hipLaunchKernelGGL((dev::k_push_combine<P, T, U, V, E, decltype(vp_c)::value>), dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, pa, Asrc,
                              (const int32_t*)d_list, nf, (const unsigned int*)d_off, (const T*)x, (const V*)d_vp, d_best, (const uint32_t*)d_want, d_touched,

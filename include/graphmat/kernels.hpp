@@ -3554,18 +3554,19 @@ k_push_bid_bits(gm_csr_t S /* rows = sources */, const uint32_t* __restrict__ ac
   }
 }
 
-// Top-down step of a REDUCE_COMMUTATIVE program with a 4-byte reduction type (SSSP distances,
-// labels, counts): every out-edge of the active set evaluates its message and folds it into the
-// destination's slot of `acc` -- (1 << 32 | value bits), 0 = empty, because there is no additive
-// identity: the first message assigns -- with a compare-and-swap loop around the user's
-// reduce_function.  Any order is fine for such programs, so the result is the pull's.
+// Top-down step of a REDUCE_COMMUTATIVE program with a reduction type of at most 4 bytes (SSSP
+// distances, labels, counts; 8- and 16-bit ones in the low bytes of the slot): every out-edge of
+// the active set evaluates its message and folds it into the destination's slot of `acc` --
+// (1 << 32 | value bits), 0 = empty, because there is no additive identity: the first message
+// assigns -- with a compare-and-swap loop around the user's reduce_function.  Any order is fine
+// for such programs, so the result is the pull's.
 template <class P, class T, class U, class V, class E, bool USE_VP>
 __global__ void __launch_bounds__(kBlock)
 k_push_combine(ProgArg<P> pa, gm_csr_t S /* rows = sources */, const int32_t* __restrict__ list, int nlist,
                const unsigned int* __restrict__ off, const T* __restrict__ x, const V* __restrict__ vp,
                unsigned long long* __restrict__ acc, const uint32_t* __restrict__ want, int32_t* __restrict__ touched,
                unsigned int* __restrict__ tcount) {
-  static_assert(sizeof(U) == 4, "packed (flag, value) slots need a 4-byte reduction type");
+  static_assert(sizeof(U) <= 4, "packed (flag, value) slots hold a reduction type of at most 4 bytes");
   const P& p = *reinterpret_cast<const P*>(pa.b);
   int u;
   int64_t e0, e1;
@@ -3589,11 +3590,11 @@ k_push_combine(ProgArg<P> pa, gm_csr_t S /* rows = sources */, const int32_t* __
           U folded = res;
           if (old != 0ull) {
             const uint32_t ob = (uint32_t)old;
-            memcpy(&folded, &ob, 4);
+            memcpy(&folded, &ob, sizeof(U));
             p.P::reduce_function(folded, res);
           }
-          uint32_t fb;
-          memcpy(&fb, &folded, 4);
+          uint32_t fb = 0u;
+          memcpy(&fb, &folded, sizeof(U));
           const unsigned long long neu = (1ull << 32) | (unsigned long long)fb;
           if (neu == old) break;  // the message changes nothing
           const unsigned long long seen = atomicCAS(&acc[c], old, neu);

@@ -801,7 +801,7 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  * neither keeps anything in these slots from one call to the next (each writes everything it reads there, every call), so
  * their uses never live in one run; like all runs on one graph, the calls follow each other on one stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
- * exact commutative ones of 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
+ * exact commutative ones of at most 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
  * one wave per row (larger ones, which no products stream can hold) and never ask for GM_WS_GIANT_TERMS: that is the
  * float sums' and the ordered folds' stream.  A run whose probed a=b / commutative strategy fails its cross-check falls
  * back to the ordered fold, and with the same step gives up top-down steps for good.  gm_run_sgd_bipartite
