@@ -14,6 +14,7 @@
 #include <string>
 
 #include "GraphMatRuntime.h"
+#include "gm_build.hpp"  // the layout options that gm_set_option / gm_reset_options write
 #include "gm_internal.hpp"
 #include "gm_run_fixed.hpp"
 
@@ -21,7 +22,6 @@
 
 namespace gm {
 
-extern int g_short_row, g_giant_row, g_rank_by, g_rank_cap, g_col_tiles, g_tile_min_row, g_long_mid, g_tile_balance, g_own_wave_row, g_sort_tile_lists, g_sweep_slices, g_sweep_acc_limit, g_sweep_long_limit, g_sweep_long_row, g_sweep_fold_share, g_sweep_border_factor, g_blocked_rows, g_sweep_waves, g_sweep_stream, g_sweep_stream_weight;
 int g_force_ordered = 0;  // (read by gm_lda.hip as well)
 extern int g_lda_tile;
 extern int g_tc_form;

@@ -1433,7 +1433,7 @@ k_spmv_rowwave(ProgArg<P> pa, gm_csr_t A, const T* __restrict__ x, U* __restrict
 
 // ------------------------------------------------------------------------------------
 // The rows of more than GM_SHORT_ROW edges that are not giant, in ONE launch per set: the row-stationary sweep over a
-// sliced-ELLPACK layout (graphmat_hip.h: gm_sweep_t; built by gm_graph.hip: build_sweep; prototype and measurements:
+// sliced-ELLPACK layout (graphmat_hip.h: gm_sweep_t; built by gm_graph_sweep.hip: build_sweep; prototype and measurements:
 // tools/sell_bench.hip, profiles/r05_sell_prototype*.txt -- RMAT-26: 876 M edges in 2.05 ms against 2.25 ms for 679 M of them
 // in round 4's CSR-ordered sweep plus 1.2 ms of one-wave-per-row tile passes for the rest).
 // Workgroup w (one per CU, 16 waves) owns the rows of length rank r % 256 == w and keeps their running values in LDS (medium
@@ -2116,7 +2116,7 @@ k_spmv_sell_sharded(ProgArg<P> pa, int set, int stage_words, int nslices, int nr
 }
 
 // ------------------------------------------------------------------------------------
-// The short rows of a graph WITHOUT skew as a column-blocked stream (graphmat_hip.h: gm_blocked_t; built by gm_graph.hip:
+// The short rows of a graph WITHOUT skew as a column-blocked stream (graphmat_hip.h: gm_blocked_t; built by gm_graph_blocked.hip:
 // build_blocked; prototype and measurements: tools/blocked_bench.hip, profiles/r05_short_rows_blocked_stream_prototype.md --
 // uniform 16-out-regular 2^26: 9.0-9.5 ms against 21 ms for the row-blocks, whose every gather misses).
 // Workgroup b of a pass owns GM_BLOCKED_ROWS short rows and keeps their running values in LDS from the first slice to the last; the
