@@ -1369,6 +1369,31 @@ class Run {
     launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, A, xq, xb, (const V*)d_vp, y, yb_write, acc_flags, rk, rowfilter);
   }
 
+  // the bits of the engine option sweep_form (graphmat_hip.h: gm_engine_options_t describes them)
+  enum : int {
+    SF_SHORTS_PLACE = 3,       // bits 0-1: where the short rows' pass runs (0 and 3 in front of the sweep, 1 beside it, 2 behind it)
+    SF_STAGE_ROUNDS = 4,       // bit 2: the long rows staged in rounds of 1024 entries
+    SF_GIANTS_OWN = 8,         // bit 3: the giant rows gather for themselves
+    SF_GIANTS_SLICED = 16,     // bit 4: their gathers in k_giant_gather_sliced behind the sweep
+    SF_NO_SPARSE = 32,         // bit 5: a sparse x does not take the sweep
+    SF_SPARSE_ANY_SIZE = 64,   // bit 6: it does on graphs of any size
+    SF_NO_SHORT_STREAM = 128,  // bit 7: the short rows keep the row-block kernel
+    SF_SHORT_STREAM_ANY = 256, // bit 8: they ride the sweep whatever their number
+    SF_NO_FOLD_APPLY = 512     // bit 9: their fold never applies and sends
+  };
+  // the sweep kernels (kernels.hpp): k_spmv_sell, k_spmv_sell_stream (the launch that holds the short rows' stream groups), k_spmv_sell_w12,
+  // k_spmv_sell_sparse, k_spmv_sell_sharded
+  enum SweepKernel { SWEEP_NONE, SWEEP_PLAIN, SWEEP_STREAM, SWEEP_W12, SWEEP_SPARSE, SWEEP_SHARDED };
+  // Which of them takes this structure and message vector (never SWEEP_STREAM: that is the schedule's choice for the plain form's first
+  // launch): a block's groups are dealt over 16 waves, or over 12 for the 768-thread form; a shard's structure and a sparse x have the
+  // 16-wave form only, and a sparse x single-shard structures only.  SWEEP_NONE: no kernel here walks it.
+  static SweepKernel sweep_kernel(const gm_sweep_t& sw, bool sparse_x) {
+    const bool waves16 = sw.waves == 0 || sw.waves == 16;
+    if (sw.nsub > 1) return waves16 && !sparse_x ? SWEEP_SHARDED : SWEEP_NONE;
+    if (sparse_x) return waves16 ? SWEEP_SPARSE : SWEEP_NONE;
+    return waves16 ? SWEEP_PLAIN : sw.waves == 12 ? SWEEP_W12 : SWEEP_NONE;
+  }
+
   // Can this run's pull multiply of the OUT adjacency take the row-stationary sweep (graphmat_hip.h: gm_sweep_t; kernels.hpp:
   // k_spmv_sell)?  Every x entry present, 2-operand program, 4-byte messages and reductions, edge values absent or 4 bytes and
   // carried by the structure, no row filter, nothing accumulated from an earlier pass; the structure must hold exactly the rows
@@ -1383,13 +1408,12 @@ class Run {
       // a shard's rows (gm_sweep_t.nsub): the structure must describe THIS cut of the message vector; a single-shard structure is not
       // used by a run that exchanges messages (a world of one rank: nothing to gain)
       if (sw->nsub > 1 ? (sw->nsub != desc.nshards || sw->stride != n || sw->hot_words <= 0) : multi) return false;
-      if (sw->waves != 0 && sw->waves != 16 && !(sw->waves == 12 && sw->nsub <= 1)) return false;  // (a block's groups dealt over a wave count no kernel here has)
+      if (sweep_kernel(*sw, xb != nullptr) == SWEEP_NONE) return false;  // (a block's groups dealt over a wave count no kernel here has)
       // a SPARSE message vector (ACTIVE_ONLY programs; round 6): k_spmv_sell_sparse -- single-shard structures, 16 waves, not under the static presence bits of a dense x
       // (large graphs only -- the sweep walks all its slices however few columns are present: unchanged SSSP.cpp RMAT-22 6.5 -> 12.3 ms and
       // RMAT-23 11.5 -> 14.4 ms when it was taken there, 21.6 -> 20.0 ms at RMAT-24, 84 -> 60 ms at RMAT-26; sweep_form bit 6 lifts the size
       // limit for tests, bit 5 refuses the form)
-      if (xb != nullptr && (sw->nsub > 1 || (sw->waves != 0 && sw->waves != 16) || (acc & dev::ACC_STATIC_BITS) || (opt.sweep_form & 32) ||
-                            (Aout.nnz < 200000000ll && !(opt.sweep_form & 64)))) return false;
+      if (xb != nullptr && ((acc & dev::ACC_STATIC_BITS) || (opt.sweep_form & SF_NO_SPARSE) || (Aout.nnz < 200000000ll && !(opt.sweep_form & SF_SPARSE_ANY_SIZE)))) return false;
       if (Aout.vals != nullptr && !(sw->val_bytes == 4 && sizeof(E) == 4 && std::is_trivially_copyable<E>::value)) return false;
       return true;
     } else {
@@ -1414,175 +1438,239 @@ class Run {
     return (const uint32_t*)pm;
   }
 
-  // The OUT adjacency through the sweep: the giant rows' passes (products spread over the chip, then the exact replay or the
-  // ordered fold: a chain of small latency-bound launches) on the auxiliary stream from the moment x is complete, the short
-  // rows (row-blocks of the whole-graph CSR) and the sweep's launches on the main stream; joined before apply.  sweep_form:
-  // 0 = short rows in front of the sweep, 1 = on the auxiliary stream behind the giant passes (next to the sweep), 2 = behind
-  // the sweep.  The three row sets are disjoint, so no two kernels touch the same y entry.
+  // ---- the OUT adjacency through the sweep ---------------------------------------------------------------------------------------------
+  // Three disjoint row sets, so no two kernels touch the same y entry: the sweep's rows (its launches, one per set, on the main stream), the
+  // giant rows (products spread over the chip, then the exact replay or the ordered fold: a chain of small latency-bound launches, always on
+  // the auxiliary stream) and the short rows.  What one multiply does with the last two is a SweptSchedule, decided before the first launch.
+  enum ShortRows {     // the short rows: row-blocks of the whole-graph CSR unless said otherwise
+    SHORTS_FRONT,      // on the main stream in front of the sweep (sweep_form bits 0-1 = 0, the default, and 3)
+    SHORTS_BESIDE,     // on the auxiliary stream behind what the giant rows run there, next to the sweep (bits 0-1 = 1; always with the 768-thread form)
+    SHORTS_BEHIND,     // on the main stream behind the sweep, next to the giant rows' fold passes (bits 0-1 = 2; always when the giant rows' products are gathered for them)
+    SHORTS_BLOCKED,    // the column-blocked stream (gm_blocked_t) after the join, whenever the graph has one: it wants the whole chip
+    SHORTS_FOLDED      // the sweep's first launch gathers for them too (gm_sweep_t.nstream), k_short_fold folds its products behind the sweep
+  };
+  enum GiantRows {
+    GIANTS_NONE,           // the graph has none
+    GIANTS_OWN,            // their own gathers and folds from the fork, beside everything: no two-pass float sum, a sparse x, a structure without their entries, sweep_form bit 3
+    GIANTS_SWEEP_GATHERS,  // the sweep's first launch gathers their products, the fold passes run behind it (the default for float sums)
+    GIANTS_SLICED_BEHIND,  // k_giant_gather_sliced and the fold passes behind the sweep (sweep_form bit 4)
+    GIANTS_SLICED_BESIDE   // k_giant_gather_sliced and the fold passes from the fork, beside the sweep (the 768-thread form)
+  };
+  struct SweptSchedule {
+    ShortRows shorts;
+    GiantRows giants;
+    SweepKernel first, rest;  // the kernel of the first launch (set 0) and of the others
+    int stage;                // LDS words of the long rows' stage
+    bool fold_applies;        // SHORTS_FOLDED: the fold applies its rows and sends for them, given the mask of the other rows (fold_rest_mask)
+    U* gterms;                // the giant rows' products stream (GM_WS_GIANT_TERMS) unless GIANTS_NONE / GIANTS_OWN
+    U* sterms;                // SHORTS_FOLDED: the short rows' products stream (GM_WS_SHORT_TERMS)
+    gm_blocked_t bl;          // SHORTS_BLOCKED: the stream
+    bool giants_beside() const { return giants == GIANTS_OWN || giants == GIANTS_SLICED_BESIDE; }
+    bool giants_behind() const { return giants == GIANTS_SWEEP_GATHERS || giants == GIANTS_SLICED_BEHIND; }
+    bool giants_sliced() const { return giants == GIANTS_SLICED_BEHIND || giants == GIANTS_SLICED_BESIDE; }
+  };
+  // (k_short_fold's fused form is instantiated for such vertex properties only)
+  static constexpr bool kFoldApplyTypes = std::is_trivially_copyable<V>::value && sizeof(V) <= 16;
+
+  // The schedule of this multiply (acc, sw, defer_join: multiply_out_swept's).  Asks the graph for the two products streams: a stream it
+  // cannot give leaves its rows to their own kernels.
+  SweptSchedule swept_schedule(int acc, const gm_sweep_t& sw, bool defer_join) {
+    SweptSchedule sc{};
+    const bool sparse_x = xb != nullptr;
+    // Giant rows.  Their fold passes read a products stream (gm_csr_t.gterm_off); when the reduction has such a two-pass form
+    // (float sums: the exact replay; plain ordered folds) the SWEEP gathers for them -- slice by slice, with its LDS hot sets,
+    // a slice's giant edges dealt evenly over the workgroups -- and only the fold passes remain, on the auxiliary stream next to
+    // the short rows' pass BEHIND the sweep.  (Round 5, first form: k_giant_terms gathered the 36 M giant-row messages of
+    // RMAT-26 untiled -- 64 % L2 misses -- on the auxiliary stream next to the short rows' kernel, which it stretched from 1.27
+    // to 1.55 ms.)  sweep_form bit 3 keeps that first form; other reductions (commutative) gather in their own kernels as before.
+    if constexpr (dev::stageable<U>::value) {
+      // (float sums only.  A plain ordered fold of a giant row is a chain of dependent reduce_function calls -- 4-5 ms for RMAT-26's
+      // hub row -- that has to start as early as possible: such programs keep the first form, k_giant_terms and the fold on the
+      // auxiliary stream from the moment x is complete, next to the short rows AND the sweep; unchanged PageRank.cpp, RMAT-26:
+      // 459 ms with its chain behind the sweep, 444 with it beside everything)
+      const bool two_pass = rk == REDUCE_F32_ADD && std::is_same<U, float>::value;
+      void* p6 = nullptr;
+      if (two_pass && !sparse_x && Aout.ngiant > 0 && sw.ngiant_edges > 0 && sw.gcol != nullptr && !(opt.sweep_form & SF_GIANTS_OWN) &&
+          gm_graph_workspace(g, GM_WS_GIANT_TERMS, (size_t)Aout.giant_edges * sizeof(U) + 64, &p6) == GM_OK)
+        sc.gterms = (U*)p6;
+    }
+    // (a graph with few busy rows and a column-blocked stream of its short rows, graphmat_hip.h: gm_blocked_t: the stream instead of the
+    // row-blocks, on the main stream -- it wants the whole chip, like the sweep)
+    const bool shorts_blocked = blocked_usable(acc, &sc.bl);
+    // The 768-thread form (gm_sweep_t.waves = 12; experiment of round 6): the sweep leaves every CU a quarter of its registers and 36 KB of LDS,
+    // and EVERYTHING else runs beside it on the auxiliary stream from the moment x is complete: the giant rows' gathers in slice order
+    // (k_giant_gather_sliced), their fold passes, then the short rows' kernel.  (Not in front of the column-blocked stream or a deferred
+    // join: the plain kernel walks such a structure then.)
+    sc.rest = sweep_kernel(sw, sparse_x);
+    if (sc.rest == SWEEP_W12 && (shorts_blocked || defer_join)) sc.rest = SWEEP_PLAIN;
+    const bool w12 = sc.rest == SWEEP_W12;
+    // (the giant rows' gathers in a kernel of their own instead of inside the sweep: sweep_form bit 4, or the 768-thread form)
+    sc.giants = Aout.ngiant <= 0                                              ? GIANTS_NONE
+                : sc.gterms == nullptr                                        ? GIANTS_OWN
+                : w12                                                         ? GIANTS_SLICED_BESIDE
+                : (sw.nsub <= 1 && (opt.sweep_form & SF_GIANTS_SLICED) != 0) ? GIANTS_SLICED_BEHIND
+                                                                              : GIANTS_SWEEP_GATHERS;
+    // The short rows through the sweep (gm_sweep_t.nstream; round 6, last session): their edges sit in STREAM groups of the first launch's
+    // blocks, the sweep gathers for them -- from ~1.3 MB of x at a time and its LDS hot sets, where the row-block kernel gathers from the
+    // whole message vector -- and leaves the products in a stream that k_short_fold folds bin by bin behind the sweep.  Dense x, 16 waves
+    // (a shard's structure too); sweep_form bit 7 keeps the row-block kernel (every other form walks wrow, which leaves the groups out).
+    // From 2^25 short-row edges on (bit 8: on any structure -- tests): below, the blocks' few stream rows cost the sweep more than the row-block
+    // kernel saves -- RMAT-23 (27 M) 0.595 -> 0.610 ms, a shard of 8 of RMAT-26 (20 M) 0.82 -> 0.89; RMAT-24 (53 M) 1.049 -> 0.946, a shard of 4 (40 M) 1.28 -> 1.25,
+    // of 2 (81 M) 2.25 -> 1.92, RMAT-25 (107 M) 2.08 -> 1.76, RMAT-26 3.78 -> 3.28, RMAT-27 9.35 -> 7.34 (with the stream rows weighted 3 : 1 in the waves' shares).
+    if (sw.nstream > 0 && sw.sinv != nullptr && sw.wrow_stream != nullptr && !sparse_x && !w12 && !shorts_blocked && !(opt.sweep_form & SF_NO_SHORT_STREAM) &&
+        sw.bin_cap == GM_STREAM_BIN && (sw.nstream >= (1ll << 25) || (opt.sweep_form & SF_SHORT_STREAM_ANY))) {
+      void* p16 = nullptr;
+      if (gm_graph_workspace(g, GM_WS_SHORT_TERMS, (size_t)sw.nstream_slots * sizeof(U) + 256, &p16) == GM_OK) sc.sterms = (U*)p16;
+    }
+    const int place = opt.sweep_form & SF_SHORTS_PLACE;
+    sc.shorts = sc.sterms != nullptr    ? SHORTS_FOLDED
+                : shorts_blocked        ? SHORTS_BLOCKED
+                : w12                   ? SHORTS_BESIDE
+                : sc.gterms != nullptr  ? SHORTS_BEHIND
+                : place == 1            ? SHORTS_BESIDE
+                : place == 2            ? SHORTS_BEHIND
+                                        : SHORTS_FRONT;
+    // (the launch that holds the short rows' stream groups walks the wave ranges that include them and stores their products)
+    sc.first = (sc.rest == SWEEP_PLAIN && sc.sterms != nullptr) ? SWEEP_STREAM : sc.rest;
+    // the pool of LDS words is split between the slice's hot entries and the long rows' stage: a stage that takes the
+    // largest block in one round where that leaves most of the pool to the hot set
+    sc.stage = 64;
+    if (sw.nrows_long > 0) {
+      sc.stage = (sw.max_long_block + 63) / 64 * 64;
+      if (sc.stage > GM_SWEEP_MAX_STAGE) sc.stage = GM_SWEEP_MAX_STAGE;
+      if (sc.stage < 1024) sc.stage = 1024;
+      if (opt.sweep_form & SF_STAGE_ROUNDS) sc.stage = 1024;  // (tests: blocks staged in several rounds)
+    }
+    if (w12 && sc.stage > GM_SWEEP_MAX_STAGE_W12) sc.stage = GM_SWEEP_MAX_STAGE_W12;
+    // Fold + apply + send (sweep_form bit 9 refuses it).  The fold writes x in place, so nothing of this multiply may read x beside or behind
+    // it: one shard, all sweep launches in front of it on this stream, the giant rows' products gathered by the sweep (their passes on the
+    // auxiliary stream then read the products stream only: k_giant_sums / k_giant_maps / k_giant_replay_maps, launch_spmv's two-pass float
+    // form WITH piece maps -- without maps k_spmv_giant gets x), no column-blocked tail, no cross-check of a probed strategy (it folds sampled
+    // rows again from x).  The rows that are neither short nor without in-edges are applied by step_pull behind the join (fold_rest_mask).
+    if constexpr (kFoldApplyTypes) {
+      const bool giants_off_x = sc.giants == GIANTS_NONE || (sc.giants == GIANTS_SWEEP_GATHERS && opt.giant_maps != 0 && Aout.gchunk_state != nullptr);
+      sc.fold_applies = sc.shorts == SHORTS_FOLDED && fold_apply_want && !(opt.sweep_form & SF_NO_FOLD_APPLY) && sw.nsub <= 1 && !multi && !defer_join &&
+                        (acc & dev::ACC_STATIC_BITS) && giants_off_x && !rk_unverified && d_want == nullptr && xq == (const T*)x;
+    }
+    return sc;
+  }
+
+  // the giant rows' chain on the auxiliary stream (forked by the caller): k_giant_gather_sliced where the schedule says so, then their passes --
+  // the fold passes only when the products are in their stream already
+  void swept_giant_rows(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, const SweptSchedule& sc) {
+    if (sc.giants_sliced()) {
+      with_edge_values<E>(Aout.vals != nullptr && sw.gval != nullptr, [&](auto hv) {
+        constexpr bool HV = decltype(hv)::value;
+        hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, HV>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, HV ? sw.gval : (const uint32_t*)nullptr, sw.gdst,
+                           (int64_t)sw.ngiant_edges, xq, sc.gterms);
+      });
+      st.spmv_launches++;
+    }
+    gm_csr_t Ag = Aout;
+    Ag.nblk = 0; Ag.nmid = 0; Ag.nmid_long = 0;
+    Launch Lg = launch_ctx();
+    Lg.terms_ready = sc.gterms != nullptr;
+    launch_spmv_vp<P, T, U, V, E>(use_vp, Lg, pa, Ag, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+  }
+  // the short rows' row-block pass, on the main stream or (SHORTS_BESIDE) on the auxiliary stream, which the join then waits for
+  void swept_short_rows(const dev::ProgArg<P>& pa, int acc, bool on_aux) {
+    gm_csr_t As = Aout;
+    As.nmid = 0; As.nmid_long = 0; As.ngiant = 0; As.ngchunk = 0;
+    if (As.nblk <= 0) return;
+    Launch La = launch_ctx();
+    La.aux = nullptr;
+    La.tiled_untiled_pass = true;
+    if (on_aux) { La.s = aux.s; La.timer = nullptr; }
+    launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, As, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+    if (on_aux) { GM_HIP_OK(hipEventRecord(aux.join, aux.s)); aux.pending = true; }
+  }
+  // SHORTS_FOLDED: the short rows' fold from the products the sweep left (next to the giant rows' fold passes on the auxiliary stream)
+  void swept_short_fold(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, const SweptSchedule& sc) {
+    bool fused_fold = false;
+    if constexpr (kFoldApplyTypes) {
+      if (sc.fold_applies && fold_rest_mask(sw) != nullptr) {
+        hipLaunchKernelGGL((dev::k_short_fold<P, U, T, V, true>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sc.sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap,
+                           sw.sbin_row, sw.soff, sw.srow, y, (uint32_t*)nullptr, d_vp, x, desc.row_lo);
+        fused_fold = true;
+        fold_applied = true;
+        fold_applies++;
+        if (verbose && !said_fold_apply) { printf("GraphMat(HIP):   the fold applies its rows and sends their next messages (k_short_fold, fused; no pass over y for them)\n"); said_fold_apply = true; }
+      }
+    }
+    if (!fused_fold)
+      hipLaunchKernelGGL((dev::k_short_fold<P, U>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sc.sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap, sw.sbin_row,
+                         sw.soff, sw.srow, y, (acc & dev::ACC_STATIC_BITS) ? (uint32_t*)nullptr : ybits);
+    st.spmv_launches++;
+    short_folds++;
+    if (verbose && !said_short_fold) { printf("GraphMat(HIP):   the rows of up to %d edges ride the sweep (k_short_fold)\n", (int)sw.short_row); said_short_fold = true; }
+    timer.mark(TAG_ROWBLOCK);  // (the short rows' share of the multiply that is not inside the sweep)
+  }
+  // launch `set` of the sweep: the kernel's leading arguments are the same in every form, and all but the sparse form gather for the giant rows
+  // (gt: their products stream, in the launch that does)
+  void swept_launch(const dev::ProgArg<P>& pa, const gm_sweep_t& sw, const SweptSchedule& sc, int set) {
+    const SweepKernel kernel = set == 0 ? sc.first : sc.rest;
+    U* gt = (set == 0 && sc.giants == GIANTS_SWEEP_GATHERS) ? sc.gterms : (U*)nullptr;
+    const bool stores = set == 0 && sc.sterms != nullptr;  // (a shard's kernel takes the stream groups as arguments)
+    with_edge_values<E>(Aout.vals != nullptr, [&](auto hv) {
+      constexpr bool HV = decltype(hv)::value;
+      const uint32_t *sval = HV ? sw.sval : nullptr, *lval = HV ? sw.lval : nullptr, *gval = HV ? sw.gval : nullptr;
+      auto launch = [&](auto k, unsigned threads, const uint32_t* rows, auto... tail) {
+        hipLaunchKernelGGL(k, dim3(256), dim3(threads), 0, s, pa, set, sc.stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, rows, sw.row_of_slot, sw.lcol, lval, sw.lps,
+                           sw.lrow_of_slot, tail...);
+      };
+      auto launch_giants = [&](auto k, unsigned threads, const uint32_t* rows, auto... tail) { launch(k, threads, rows, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, tail...); };
+      switch (kernel) {
+        case SWEEP_SHARDED:  // a shard's rows: the message vector is made of nsub owners' ranges
+          launch_giants(&dev::k_spmv_sell_sharded<P, T, U, V, E, HV>, 1024, stores ? sw.wrow_stream : sw.wrow, sw.nsub, sw.stride, sw.hot_words, stores ? sc.sterms : (U*)nullptr);
+          break;
+        case SWEEP_SPARSE:  // a sparse message vector: presence tests per entry, y's presence bits OR-ed in
+          if (verbose && !said_sparse_sweep) { printf("GraphMat(HIP):   sparse message vector through the sweep (k_spmv_sell_sparse)\n"); said_sparse_sweep = true; }
+          if (set == 0) sparse_sweeps++;
+          launch(&dev::k_spmv_sell_sparse<P, T, U, V, E, HV>, 1024, sw.wrow, xq, xb, y, ybits);
+          break;
+        case SWEEP_W12:  // 768-thread workgroups
+          launch_giants(&dev::k_spmv_sell_w12<P, T, U, V, E, HV>, 768, sw.wrow);
+          break;
+        case SWEEP_STREAM:  // the launch that holds the short rows' stream groups stores their products
+          launch_giants(&dev::k_spmv_sell_stream<P, T, U, V, E, HV>, 1024, sw.wrow_stream, sc.sterms);
+          break;
+        default:
+          launch_giants(&dev::k_spmv_sell<P, T, U, V, E, HV>, 1024, sw.wrow);
+      }
+    });
+  }
+
+  // One multiply: fork; what runs beside the sweep; the sweep's launches; what runs behind it; join; the column-blocked stream; the cross-check
+  // of a probed strategy.
   // defer_join: return without waiting for the auxiliary stream (the giant rows' fold passes): the caller joins (aux.wait_join) before it
   // touches the giant rows' y entries -- the sharded swept schedule applies, sends and starts exchanging all other rows meanwhile
   void multiply_out_swept(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, bool defer_join = false) {
     if constexpr (sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<T>::value && std::is_trivially_copyable<U>::value) {
-      const Launch L = launch_ctx();
-      aux.keep = true;
-      aux.pending = false;
-      // Giant rows.  Their fold passes read a products stream (gm_csr_t.gterm_off); when the reduction has such a two-pass form
-      // (float sums: the exact replay; plain ordered folds) the SWEEP gathers for them -- slice by slice, with its LDS hot sets,
-      // a slice's giant edges dealt evenly over the workgroups -- and only the fold passes remain, on the auxiliary stream next to
-      // the short rows' pass BEHIND the sweep.  (Round 5, first form: k_giant_terms gathered the 36 M giant-row messages of
-      // RMAT-26 untiled -- 64 % L2 misses -- on the auxiliary stream next to the short rows' kernel, which it stretched from 1.27
-      // to 1.55 ms.)  sweep_form bit 3 keeps that first form; other reductions (commutative) gather in their own kernels as before.
-      U* gterms = nullptr;
-      if constexpr (dev::stageable<U>::value) {
-        // (float sums only.  A plain ordered fold of a giant row is a chain of dependent reduce_function calls -- 4-5 ms for RMAT-26's
-        // hub row -- that has to start as early as possible: such programs keep the first form, k_giant_terms and the fold on the
-        // auxiliary stream from the moment x is complete, next to the short rows AND the sweep; unchanged PageRank.cpp, RMAT-26:
-        // 459 ms with its chain behind the sweep, 444 with it beside everything)
-        const bool two_pass = rk == REDUCE_F32_ADD && std::is_same<U, float>::value;
-        void* p6 = nullptr;
-        if (two_pass && xb == nullptr && Aout.ngiant > 0 && sw.ngiant_edges > 0 && sw.gcol != nullptr && !(opt.sweep_form & 8) &&
-            gm_graph_workspace(g, GM_WS_GIANT_TERMS, (size_t)Aout.giant_edges * sizeof(U) + 64, &p6) == GM_OK)
-          gterms = (U*)p6;
-      }
-      GM_HIP_OK(hipEventRecord(aux.fork, s));
-      GM_HIP_OK(hipStreamWaitEvent(aux.s, aux.fork, 0));
-      aux.forked = true;
-      gm_csr_t Ag = Aout;
-      Ag.nblk = 0; Ag.nmid = 0; Ag.nmid_long = 0;
-      if (Aout.ngiant > 0 && gterms == nullptr) launch_spmv_vp<P, T, U, V, E>(use_vp, L, pa, Ag, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
-      gm_csr_t As = Aout;  // the short rows
-      As.nmid = 0; As.nmid_long = 0; As.ngiant = 0; As.ngchunk = 0;
-      Launch La = L;
-      La.aux = nullptr;
-      La.tiled_untiled_pass = true;
-      // (a graph with few busy rows and a column-blocked stream of its short rows, graphmat_hip.h: gm_blocked_t: the stream instead of the
-      // row-blocks, on the main stream -- it wants the whole chip, like the sweep)
-      gm_blocked_t bl;
-      const bool shorts_blocked = blocked_usable(acc, &bl);
-      // The 768-thread form (gm_sweep_t.waves = 12; experiment of round 6): the sweep leaves every CU a quarter of its registers and 36 KB of LDS,
-      // and EVERYTHING else runs beside it on the auxiliary stream from the moment x is complete: the giant rows' gathers in slice order
-      // (k_giant_gather_sliced), their fold passes, then the short rows' kernel.
-      const bool w12 = sw.waves == 12 && sw.nsub <= 1 && !shorts_blocked && !defer_join && xb == nullptr;
-      // (the giant rows' gathers in a kernel of their own instead of inside the sweep: sweep_form bit 4, or the 768-thread form)
-      const bool gather_apart = gterms != nullptr && sw.nsub <= 1 && ((opt.sweep_form & 16) != 0 || w12);
-      auto giant_gather = [&]() {
-        with_edge_values<E>(Aout.vals != nullptr && sw.gval != nullptr, [&](auto hv) {
-          constexpr bool HV = decltype(hv)::value;
-          hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, HV>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, HV ? sw.gval : (const uint32_t*)nullptr, sw.gdst,
-                             (int64_t)sw.ngiant_edges, xq, gterms);
-        });
-        st.spmv_launches++;
-      };
-      bool chain_done = false;
-      if (w12 && gterms != nullptr) {  // gathers and fold passes of the giant rows right away, beside the sweep
-        giant_gather();
-        Launch Lg = L;
-        Lg.terms_ready = true;
-        launch_spmv_vp<P, T, U, V, E>(use_vp, Lg, pa, Ag, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
-        chain_done = true;
-      }
-      // The short rows through the sweep (gm_sweep_t.nstream; round 6, last session): their edges sit in STREAM groups of the first launch's
-      // blocks, the sweep gathers for them -- from ~1.3 MB of x at a time and its LDS hot sets, where the row-block kernel gathers from the
-      // whole message vector -- and leaves the products in a stream that k_short_fold folds bin by bin behind the sweep.  Dense x, 16 waves
-      // (a shard's structure too); sweep_form bit 7 keeps the row-block kernel (every other form walks wrow, which leaves the groups out).
-      // From 2^25 short-row edges on (bit 8: on any structure -- tests): below, the blocks' few stream rows cost the sweep more than the row-block
-      // kernel saves -- RMAT-23 (27 M) 0.595 -> 0.610 ms, a shard of 8 of RMAT-26 (20 M) 0.82 -> 0.89; RMAT-24 (53 M) 1.049 -> 0.946, a shard of 4 (40 M) 1.28 -> 1.25,
-      // of 2 (81 M) 2.25 -> 1.92, RMAT-25 (107 M) 2.08 -> 1.76, RMAT-26 3.78 -> 3.28, RMAT-27 9.35 -> 7.34 (with the stream rows weighted 3 : 1 in the waves' shares).
-      U* sterms = nullptr;
-      if (sw.nstream > 0 && sw.sinv != nullptr && sw.wrow_stream != nullptr && xb == nullptr && !w12 && !shorts_blocked && !(opt.sweep_form & 128) &&
-          sw.bin_cap == GM_STREAM_BIN && (sw.nstream >= (1ll << 25) || (opt.sweep_form & 256))) {
-        void* p16 = nullptr;
-        if (gm_graph_workspace(g, GM_WS_SHORT_TERMS, (size_t)sw.nstream_slots * sizeof(U) + 256, &p16) == GM_OK) sterms = (U*)p16;
-      }
-      const int where = sterms != nullptr ? 4 : shorts_blocked ? 3 : (w12 ? 1 : (gterms != nullptr ? 2 : (opt.sweep_form & 3)));  // (3: behind everything, below; 4: folded from the sweep's products)
-      if (where == 1) { La.s = aux.s; La.timer = nullptr; }
-      auto short_rows = [&]() {
-        if (As.nblk <= 0) return;
-        launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, As, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
-        if (where == 1) { GM_HIP_OK(hipEventRecord(aux.join, aux.s)); aux.pending = true; }
-      };
-      if (where < 2) short_rows();
-      // the pool of LDS words is split between the slice's hot entries and the long rows' stage: a stage that takes the
-      // largest block in one round where that leaves most of the pool to the hot set
-      int stage = 64;
-      if (sw.nrows_long > 0) {
-        stage = (sw.max_long_block + 63) / 64 * 64;
-        if (stage > GM_SWEEP_MAX_STAGE) stage = GM_SWEEP_MAX_STAGE;
-        if (stage < 1024) stage = 1024;
-        if (opt.sweep_form & 4) stage = 1024;  // (tests: blocks staged in several rounds)
-      }
-      if (w12 && stage > GM_SWEEP_MAX_STAGE_W12) stage = GM_SWEEP_MAX_STAGE_W12;
-      for (int set = 0; set < sw.nsets; set++) {
-        U* gt = (set == 0 && !gather_apart) ? gterms : (U*)nullptr;  // (the first launch gathers for the giant rows)
-        // (the launch that holds the short rows' stream groups walks the wave ranges that include them and stores their products)
-        const uint32_t* st_rows = (sterms != nullptr && set == 0) ? sw.wrow_stream : sw.wrow;
-        U* st_terms = (sterms != nullptr && set == 0) ? sterms : (U*)nullptr;
-        with_edge_values<E>(Aout.vals != nullptr, [&](auto hv) {
-          constexpr bool HV = decltype(hv)::value;
-          const uint32_t *sval = HV ? sw.sval : nullptr, *lval = HV ? sw.lval : nullptr, *gval = HV ? sw.gval : nullptr;
-          if (sw.nsub > 1) {  // a shard's rows: the message vector is made of nsub owners' ranges (kernels.hpp: k_spmv_sell_sharded)
-            hipLaunchKernelGGL((dev::k_spmv_sell_sharded<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
-                               st_rows, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, sw.nsub, sw.stride, sw.hot_words, st_terms);
-          } else if (xb != nullptr) {  // a sparse message vector: presence tests per entry, y's presence bits OR-ed in (kernels.hpp: k_spmv_sell_sparse)
-            if (verbose && !said_sparse_sweep) { printf("GraphMat(HIP):   sparse message vector through the sweep (k_spmv_sell_sparse)\n"); said_sparse_sweep = true; }
-            if (set == 0) sparse_sweeps++;
-            hipLaunchKernelGGL((dev::k_spmv_sell_sparse<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
-                               sw.wrow, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, xq, xb, y, ybits);
-          } else if (w12) {  // 768-thread workgroups (kernels.hpp: k_spmv_sell_w12)
-            hipLaunchKernelGGL((dev::k_spmv_sell_w12<P, T, U, V, E, HV>), dim3(256), dim3(768), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, sw.wrow,
-                               sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y);
-          } else if (sterms != nullptr && set == 0) {  // the launch that holds the short rows' stream groups stores their products
-            hipLaunchKernelGGL((dev::k_spmv_sell_stream<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval,
-                               sw.wrow_stream, sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, sterms);
-          } else {
-            hipLaunchKernelGGL((dev::k_spmv_sell<P, T, U, V, E, HV>), dim3(256), dim3(1024), 0, s, pa, set, stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, sw.wrow,
-                               sw.row_of_slot, sw.lcol, lval, sw.lps, sw.lrow_of_slot, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y);
-          }
-        });
-      }
-      st.spmv_launches += sw.nsets;
-      timer.mark(TAG_WAVE);
-      if (gterms != nullptr && !chain_done) {  // the giant rows' fold passes behind the sweep, on the auxiliary stream next to the short rows
+      const SweptSchedule sc = swept_schedule(acc, sw, defer_join);
+      auto fork = [&]() {
         GM_HIP_OK(hipEventRecord(aux.fork, s));
         GM_HIP_OK(hipStreamWaitEvent(aux.s, aux.fork, 0));
-        if (gather_apart) giant_gather();
-        Launch Lg = L;
-        Lg.terms_ready = true;
-        launch_spmv_vp<P, T, U, V, E>(use_vp, Lg, pa, Ag, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+      };
+      aux.keep = true;
+      aux.pending = false;
+      fork();
+      aux.forked = true;
+      if (sc.giants_beside()) swept_giant_rows(pa, acc, sw, sc);
+      if (sc.shorts == SHORTS_FRONT || sc.shorts == SHORTS_BESIDE) swept_short_rows(pa, acc, sc.shorts == SHORTS_BESIDE);
+      for (int set = 0; set < sw.nsets; set++) swept_launch(pa, sw, sc, set);
+      st.spmv_launches += sw.nsets;
+      timer.mark(TAG_WAVE);
+      if (sc.giants_behind()) {  // (on the auxiliary stream next to the short rows)
+        fork();
+        swept_giant_rows(pa, acc, sw, sc);
       }
-      if (where == 2) short_rows();
-      if (where == 4) {  // the short rows' fold from the products the sweep left (next to the giant rows' fold passes on the auxiliary stream)
-        // Fold + apply + send (sweep_form bit 9 refuses it).  The fold writes x in place, so nothing of this multiply may read x beside or behind
-        // it: one shard, all sweep launches in front of it on this stream, the giant rows' products gathered by the sweep (their passes on the
-        // auxiliary stream then read the products stream only: k_giant_sums / k_giant_maps / k_giant_replay_maps, launch_spmv's two-pass float
-        // form WITH piece maps -- without maps k_spmv_giant gets x), no column-blocked tail, no cross-check of a probed strategy (it folds sampled
-        // rows again from x).  The rows that are neither short nor without in-edges are applied by step_pull behind the join (fold_rest_mask).
-        bool fused_fold = false;
-        if constexpr (std::is_trivially_copyable<V>::value && sizeof(V) <= 16) {
-          const bool giants_off_x = Aout.ngiant == 0 || (gterms != nullptr && !gather_apart && opt.giant_maps != 0 && Aout.gchunk_state != nullptr);
-          if (fold_apply_want && !(opt.sweep_form & 512) && sw.nsub <= 1 && !multi && !defer_join && (acc & dev::ACC_STATIC_BITS) && giants_off_x && !shorts_blocked &&
-              !rk_unverified && d_want == nullptr && xq == (const T*)x && fold_rest_mask(sw) != nullptr) {
-            hipLaunchKernelGGL((dev::k_short_fold<P, U, T, V, true>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap,
-                               sw.sbin_row, sw.soff, sw.srow, y, (uint32_t*)nullptr, d_vp, x, desc.row_lo);
-            fused_fold = true;
-            fold_applied = true;
-            fold_applies++;
-            if (verbose && !said_fold_apply) { printf("GraphMat(HIP):   the fold applies its rows and sends their next messages (k_short_fold, fused; no pass over y for them)\n"); said_fold_apply = true; }
-          }
-        }
-        if (!fused_fold)
-          hipLaunchKernelGGL((dev::k_short_fold<P, U>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap, sw.sbin_row,
-                             sw.soff, sw.srow, y, (acc & dev::ACC_STATIC_BITS) ? (uint32_t*)nullptr : ybits);
-        st.spmv_launches++;
-        short_folds++;
-        if (verbose && !said_short_fold) { printf("GraphMat(HIP):   the rows of up to %d edges ride the sweep (k_short_fold)\n", (int)sw.short_row); said_short_fold = true; }
-        timer.mark(TAG_ROWBLOCK);  // (the short rows' share of the multiply that is not inside the sweep)
-      }
+      if (sc.shorts == SHORTS_BEHIND) swept_short_rows(pa, acc, false);
+      if (sc.shorts == SHORTS_FOLDED) swept_short_fold(pa, acc, sw, sc);
       if (aux.pending && !defer_join) GM_HIP_OK(hipStreamWaitEvent(s, aux.join, 0));
       aux.keep = aux.forked = aux.pending = false;
       timer.mark(defer_join ? TAG_ROWBLOCK : TAG_GIANT);  // (the multiply ends when the auxiliary stream has joined: the wait is charged to the giant rows' passes)
-      if (shorts_blocked) {  // (with the chip to itself: its workgroups walk the slices in step only while all of them are resident)
-        launch_blocked(pa, bl);
+      if (sc.shorts == SHORTS_BLOCKED) {  // (with the chip to itself: its workgroups walk the slices in step only while all of them are resident)
+        launch_blocked(pa, sc.bl);
         st.spmv_launches += 1;
         timer.mark(TAG_ROWBLOCK);
       }

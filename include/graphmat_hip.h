@@ -698,7 +698,7 @@ typedef struct {
   int32_t giant_stream;           /* without effect since round 5 (a third stream for the giant rows' passes of round 4's tiled sweep); kept so that
                                      the fields keep their places */
   int32_t sweep_form;             /* the swept multiply (engine.hpp: multiply_out_swept): bits 0-1 = where the short rows' pass runs: 0 on the main stream
-                                     in front of the sweep (default), 1 on the auxiliary stream behind the giant rows' passes (next to the sweep),
+                                     in front of the sweep (default; 3 is taken as 0), 1 on the auxiliary stream behind the giant rows' passes (next to the sweep),
                                      2 on the main stream behind the sweep; bit 2 = the long rows staged in rounds of 1024 entries (tests); bit 3 = the
                                      giant rows gather for themselves on the auxiliary stream (k_giant_terms) instead of the sweep gathering for them; bit 4 = the giant rows' gathers in a
                                      kernel of their own behind the sweep (k_giant_gather_sliced: their entries in slice order, on the auxiliary stream next to the short rows); bit 5 = a SPARSE

@@ -398,6 +398,7 @@ def test_row_stationary_sweep_bit_exact(env, scale, tiles, threads):
     seen_sets = [1]
     #        sweep_slices, sweep_form, keep_values, own_wave_row, acc_rows, long_slots
     cases = [(0, 0, False, 4096, 10048, 512), (1, 0, False, 0, 10048, 512), (1, 1, True, 4096, 10048, 512), (1, 2, False, 0, 10048, 512), (1, 8, False, 0, 10048, 512), (1, 9, True, 4096, 10048, 512),
+             (1, 3, False, 0, 10048, 512), (1, 11, True, 4096, 10048, 512),  # (bits 0-1 = 3: the short rows run in front of the sweep, as with 0)
              (1, 0, True, 65, 10048, 512), (1, 0, False, 65, 10048, 512),  # (next to no medium rows: everything staged)
              (16, 0, False, 256, 10048, 512), (16, 4, True, 256, 10048, 512), (24, 5, False, 128, 3, 3), (128, 0, True, 512, 2, 512)]
     try:
