@@ -777,12 +777,15 @@ void launch_spmv_vp(bool use_vp, const Launch& L, const dev::ProgArg<P>& pa, con
 
 // ---- the iteration loop ---------------------------------------------------------------------------------------------
 // One run of run_graph_program (GraphMatRuntime.h:93-279) on the device.  The state of a run lives in a Run object;
-// what an iteration does is one of four SCHEDULES, each a member function that enqueues its kernels on the run's stream:
+// what an iteration does is one of these SCHEDULES, each a member function that enqueues its kernels on the run's stream:
 //   step_bits_push / step_list_push   top-down steps for small active sets (a=b and exact commutative programs)
-//   step_pull                         send (or exchange) -> multiply (plain, column-tiled on two streams, or a
-//                                     top-down bid pass over a larger active set) -> apply
+//   step_pull                         send (or exchange) -> multiply (swept, column-blocked, column-tiled on two streams,
+//                                     plain, or a top-down bid pass over a larger active set) -> apply, as a PullPlan
+//                                     decided by plan_pull before the first launch
 //   run_two_stage                     the whole fixed-count loop of a sharded ALL_VERTICES run: tail rows, then head
 //                                     rows, each multiplied / applied / sent while the other part's messages travel
+//   run_swept_sharded                 ... of one whose rows the sweep takes: the all-gather travels while the giant rows fold
+// run_loop asks choose_step which of the first three an iteration takes; every schedule applies through apply_rows.
 // d_vp / d_active cover the shard's rows in device order; x / xbits are global-size scratch, y / ybits shard-size scratch.
 template <class P, class T, class U, class V, class E>
 class Run {
@@ -808,6 +811,25 @@ class Run {
  private:
   static constexpr bool kSparseT = std::is_trivially_copyable<T>::value && sizeof(T) <= 8;
   typedef dev::sparse_entry<typename std::conditional<kSparseT, T, int>::type> xentry_t;
+
+  // ---- the small values the schedules hand each other ----------------------------------------------------------------
+  // what an iteration of run_loop does (choose_step); the kinds are the values of the notes GM_NOTE_STEP_COUNTS / GM_NOTE_STEP_KINDS
+  enum { STEP_PULL = 0, STEP_LIST = 1, STEP_BITS = 2, STEP_DENSE_PUSH = 3 };
+  struct StepChoice {
+    int kind;
+    bool xsp;  // x travels between the shards as lists of the active vertices' messages (the sparse exchange)
+  };
+  // what a multiply reads messages from
+  struct XSource {
+    const T* x;            // the message vector; null = evaluated on demand from the senders' vertex properties (lazy_send)
+    const uint32_t* bits;  // its presence words; null = every entry present
+  };
+  enum ApplyKind {
+    APPLY_STATS,        // k_apply<STEER>: sizes the next active set and lists it while it is small
+    APPLY_SEND_MASKED,  // k_apply_send_masked: the rows a mask names, and their next messages; touches neither the active vector nor the changed flag
+    APPLY_SEND,         // k_apply_send: apply and the next iteration's messages out of one pass
+    APPLY_PLAIN         // k_apply
+  };
 
   // ---- what the caller handed over -------------------------------------------------------------------------------
   P* gp;
@@ -1101,6 +1123,54 @@ class Run {
     return have ? (T*)p : nullptr;
   }
 
+  // ---- apply: the one launcher of every schedule --------------------------------------------------------------------------
+  // Rows [r0, r0 + cnt) of the shard (r0 a multiple of 32) from y, in at most max_blocks workgroups.  bits: the shard's presence words (APPLY_SEND_MASKED:
+  // the mask); want: the row-filter bits to keep current, or null; xnext: where the sending kinds write the next iteration's messages;
+  // build_list (APPLY_STATS): the changed vertices are listed as well.
+  void apply_rows(const dev::ProgArg<P>& pa, ApplyKind kind, int r0, int cnt, const uint32_t* bits, int max_blocks, uint32_t* want, T* xnext, bool build_list = false) {
+    const int grid = grid_for(cnt) < max_blocks ? grid_for(cnt) : max_blocks;
+    const U* const yr = (const U*)(y + r0);
+    const uint32_t* const br = bits + r0 / 32;
+    V* const vr = d_vp + r0;
+    uint32_t* const ar = d_active + r0 / 32;
+    switch (kind) {
+      case APPLY_STATS:
+        hipLaunchKernelGGL((dev::k_apply<P, U, V, true>), dim3(grid), dim3(dev::kBlock), 0, s, pa, yr, br, vr, ar, cnt, d_changed, Asrc.rowptr, d_striped, want,
+                           build_list ? d_list : (int32_t*)nullptr, build_list ? d_count : (unsigned int*)nullptr);
+        break;
+      case APPLY_SEND_MASKED:
+        hipLaunchKernelGGL((dev::k_apply_send_masked<P, T, U, V>), dim3(grid), dim3(dev::kBlock), 0, s, pa, yr, br, vr, cnt, xnext, desc.row_lo + r0);
+        break;
+      case APPLY_SEND:
+        hipLaunchKernelGGL((dev::k_apply_send<P, T, U, V>), dim3(grid), dim3(dev::kBlock), 0, s, pa, yr, br, vr, ar, cnt, d_changed, want, xnext, xbits, desc.row_lo + r0);
+        break;
+      case APPLY_PLAIN:
+        hipLaunchKernelGGL((dev::k_apply<P, U, V, false>), dim3(grid), dim3(dev::kBlock), 0, s, pa, yr, br, vr, ar, cnt, d_changed, (const int64_t*)nullptr,
+                           (unsigned long long*)nullptr, want, (int32_t*)nullptr, (unsigned int*)nullptr);
+        break;
+    }
+  }
+
+  // ---- what the two sharded fixed-count schedules share ---------------------------------------------------------------------
+  // before the first iteration: every live row's message into xcur, all-gathered
+  void sharded_first_messages(T* xcur) {
+    dev::ProgArg<P> pa = dev::make_prog_arg(gp);
+    timer.mark(TAG_START);
+    send_all(pa, nullptr, xcur);
+    if (gm_graph_exchange(g, GM_XCHG_MESSAGES, xcur, (int64_t)sizeof(T), xbits, nullptr) != 0) die("message exchange callback failed");
+    timer.mark(TAG_SEND);
+  }
+  // the end of iteration `it` (these schedules run at least one): the hook, the message buffers change places; behind the last iteration the
+  // graph is left all-active and the run is closed
+  void sharded_end_iteration(int it, T*& xcur, T*& xnext) {
+    gp->do_every_iteration(it);  // (the base class's empty hook: these schedules are only taken by programs that do not override it)
+    T* t = xcur; xcur = xnext; xnext = t;
+    if (it + 1 == iterations) {
+      fill_active();
+      finish(it + 1);
+    }
+  }
+
   // ---- schedule: the overlapped two-stage loop of sharded fixed-count ALL_VERTICES / OUT_EDGES runs ------------------------
   // (graphmat_hip.h: GM_XCHG_PART).  Stage 1 multiplies, applies and sends the TAIL rows (most of the rows, a third of
   // the edges) and starts their exchange; stage 2 does the same for the HEAD rows (the busy ones) while stage 1's
@@ -1168,16 +1238,10 @@ class Run {
       multiply(pa, A);
       if (join_giants) aux.wait_join(s);
       const int cnt = r1 - r0;
-      const int ag = grid_for(cnt) < dev::kApplyMaxBlocks ? grid_for(cnt) : dev::kApplyMaxBlocks;
       // apply, and -- when another iteration follows -- this part's messages of it out of the same pass (k_apply_send:
       // one launch and one read of the vertex properties less per stage; the program cannot change in between, see above)
       const bool fused = more && opt.fuse_apply_send != 0;
-      if (fused)
-        hipLaunchKernelGGL((dev::k_apply_send<P, T, U, V>), dim3(ag), dim3(dev::kBlock), 0, s, pa, (const U*)(y + r0), Aout.rowbits + r0 / 32, d_vp + r0,
-                           d_active + r0 / 32, cnt, d_changed, (uint32_t*)nullptr, xnext, xbits, desc.row_lo + r0);
-      else
-        hipLaunchKernelGGL((dev::k_apply<P, U, V, false>), dim3(ag), dim3(dev::kBlock), 0, s, pa, (const U*)(y + r0), Aout.rowbits + r0 / 32, d_vp + r0,
-                           d_active + r0 / 32, cnt, d_changed, (const int64_t*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr);
+      apply_rows(pa, fused ? APPLY_SEND : APPLY_PLAIN, r0, cnt, Aout.rowbits, dev::kApplyMaxBlocks, nullptr, xnext);
       timer.mark(TAG_APPLY);
       if (more) {
         if (!fused)
@@ -1189,13 +1253,7 @@ class Run {
       }
     };
     int it = 0;
-    {
-      dev::ProgArg<P> pa = dev::make_prog_arg(gp);
-      timer.mark(TAG_START);
-      send_all(pa, nullptr, xcur);
-      if (gm_graph_exchange(g, GM_XCHG_MESSAGES, xcur, (int64_t)sizeof(T), xbits, nullptr) != 0) die("message exchange callback failed");
-      timer.mark(TAG_SEND);
-    }
+    sharded_first_messages(xcur);
     for (; it < iterations; it++) {
       dev::ProgArg<P> pa = dev::make_prog_arg(gp);
       const bool more = it + 1 < iterations;
@@ -1209,11 +1267,8 @@ class Run {
       stage(pa, Ah, 0, rs, more, early_giants);
       if (more && gm_graph_exchange(g, GM_XCHG_WAIT, xnext, (int64_t)sizeof(T), nullptr, nullptr) != 0) die("message exchange wait failed");
       if (n_live < n) GM_HIP_OK(hipMemsetAsync(d_active + n_live / 32, 0, (size_t)(nwords - n_live / 32) * 4, s));
-      gp->do_every_iteration(it);  // (the base class's empty hook: this schedule is only taken by programs that do not override it)
-      T* t = xcur; xcur = xnext; xnext = t;
+      sharded_end_iteration(it, xcur, xnext);
     }
-    fill_active();
-    finish(it);
     return it;
   }
 
@@ -1293,9 +1348,9 @@ class Run {
   }
 
   // ---- schedule: the pull step (send -> multiply -> apply) ---------------------------------------------------------------
-  // what this iteration's multiply reads messages from (a probed strategy that fails its cross-check changes them)
-  const T* xq = nullptr;
-  const uint32_t* xb = nullptr;
+  // what the multiply being launched reads messages from: assigned by the schedules (step_pull from its plan, run_swept_sharded) and, where a probed
+  // strategy fails its cross-check, by the multiply that asked for the check
+  XSource msg{nullptr, nullptr};
 
   // sparse exchange: messages of the listed active vertices only, as (device id, message) entries
   void send_sparse(const dev::ProgArg<P>& pa) {
@@ -1322,19 +1377,19 @@ class Run {
 
   // Cross-check of a probed strategy after the first pass of a pull multiply over adjacency A whose results (presence bits
   // yb) are in y: giant rows, the first wave rows and a strided sample of all rows are folded again in order.  On a
-  // mismatch the pass is redone with the ordered fold, which also governs the rest of the run.
-  void check_probed(const dev::ProgArg<P>& pa, const gm_csr_t& A, const uint32_t* yb, const uint32_t* rowfilter, int acc_flags, uint32_t* yb_write,
-                    bool dense_x) {
-    if (!rk_unverified || (acc_flags & dev::ACC_READ_PREV)) return;
+  // mismatch the pass is redone with the ordered fold, which also governs the rest of the run.  src: what the pass read messages from;
+  // returns what the rest of the step reads them from (src, unless the redone pass had to give up messages evaluated on demand).
+  XSource check_probed(const dev::ProgArg<P>& pa, const gm_csr_t& A, const uint32_t* yb, const uint32_t* rowfilter, int acc_flags, uint32_t* yb_write, XSource src) {
+    if (!rk_unverified || (acc_flags & dev::ACC_READ_PREV)) return src;
     rk_unverified = false;
     unsigned int* d_mis = FlagBlock::at<unsigned int>(flag_v, FlagBlock::kProbeMismatch);
     GM_HIP_OK(hipMemsetAsync(d_mis, 0, 4, s));
-    const T* xc = xq;
-    const uint32_t* xbc = xb;
-    if (lazy_send) {  // the ordered fold reads materialised messages: write them once for the check
+    const bool dense_x = src.bits == nullptr;
+    XSource ordered = src;  // what the ordered fold reads
+    if (lazy_send) {        // ... materialised messages: write them once for the check
       send_all(pa, dense_x ? (const uint32_t*)nullptr : (const uint32_t*)d_active, x);
-      xc = x;
-      xbc = dense_x ? nullptr : (const uint32_t*)xbits;
+      ordered.x = x;
+      ordered.bits = dense_x ? nullptr : (const uint32_t*)xbits;
     }
     auto sample = [&](const int32_t* rows, int cnt, int stride) {
       if (cnt <= 0) return;
@@ -1342,7 +1397,7 @@ class Run {
       if constexpr ((int)program_traits<P>::reduce != (int)REDUCE_AUTO) return;  // (declared strategies are never checked)
       else
         with_flag(use_vp, [&](auto vp_c) {
-          hipLaunchKernelGGL((dev::k_check_rows<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid), dim3(dev::kBlock), 0, s, pa, A, rows, cnt, stride, xc, xbc, (const V*)d_vp,
+          hipLaunchKernelGGL((dev::k_check_rows<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid), dim3(dev::kBlock), 0, s, pa, A, rows, cnt, stride, ordered.x, ordered.bits, (const V*)d_vp,
                              (const U*)y, yb, rowfilter, d_mis);
         });
     };
@@ -1355,18 +1410,15 @@ class Run {
     GM_HIP_OK(hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, s));
     GM_HIP_OK(hipStreamSynchronize(s));
     if (verbose) printf("GraphMat(HIP):   probed reduce strategy %d cross-checked against the ordered fold: %u mismatching rows\n", rk, mis);
-    if (mis == 0) return;
+    if (mis == 0) return src;
     printf("GraphMat(HIP): warning: reduce_function matched strategy %d on the probe's operands but not on this run's data (%u sampled "
            "rows differ from the ordered fold); using the ordered fold.  Declare GraphMat::program_traits<YourProgram>::reduce to choose explicitly.\n", rk, mis);
     rk = REDUCE_ORDERED;
     can_push = false;
-    if (lazy_send) {  // the ordered kernels read materialised messages (written above for the check)
-      lazy_send = false;
-      xq = x;
-      xb = dense_x ? nullptr : (const uint32_t*)xbits;
-    }
+    lazy_send = false;  // (the ordered kernels read materialised messages, written above for the check)
     if (!(acc_flags & dev::ACC_STATIC_BITS)) GM_HIP_OK(hipMemsetAsync(yb_write, 0, (size_t)nwords * 4, s));
-    launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, A, xq, xb, (const V*)d_vp, y, yb_write, acc_flags, rk, rowfilter);
+    launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, A, ordered.x, ordered.bits, (const V*)d_vp, y, yb_write, acc_flags, rk, rowfilter);
+    return ordered;
   }
 
   // the bits of the engine option sweep_form (graphmat_hip.h: gm_engine_options_t describes them)
@@ -1398,9 +1450,9 @@ class Run {
   // k_spmv_sell)?  Every x entry present, 2-operand program, 4-byte messages and reductions, edge values absent or 4 bytes and
   // carried by the structure, no row filter, nothing accumulated from an earlier pass; the structure must hold exactly the rows
   // the whole-graph CSR's short-row pass and giant passes leave out.
-  bool sweep_usable(int acc, gm_sweep_t* sw) {
+  bool sweep_usable(int acc, XSource src, gm_sweep_t* sw) const {
     if constexpr (sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<T>::value && std::is_trivially_copyable<U>::value) {
-      if (aux.s == nullptr || use_vp || xq == nullptr || d_want != nullptr || program_row_filter<P>::enabled || (acc & dev::ACC_READ_PREV)) return false;
+      if (aux.s == nullptr || use_vp || src.x == nullptr || d_want != nullptr || program_row_filter<P>::enabled || (acc & dev::ACC_READ_PREV)) return false;
       if (!(rk == REDUCE_ORDERED || rk == REDUCE_F32_ADD || rk == REDUCE_COMMUTATIVE)) return false;
       if (opt.debug_flags & (dev::DBG_NO_TILES | dev::DBG_NO_OVERLAP)) return false;
       if (gm_graph_sweep(g, sw) != GM_OK || sw->nrows <= 0 || sw->acc_rows != GM_SWEEP_ACC_ROWS || sw->long_slots != GM_SWEEP_LONG_SLOTS) return false;
@@ -1408,16 +1460,16 @@ class Run {
       // a shard's rows (gm_sweep_t.nsub): the structure must describe THIS cut of the message vector; a single-shard structure is not
       // used by a run that exchanges messages (a world of one rank: nothing to gain)
       if (sw->nsub > 1 ? (sw->nsub != desc.nshards || sw->stride != n || sw->hot_words <= 0) : multi) return false;
-      if (sweep_kernel(*sw, xb != nullptr) == SWEEP_NONE) return false;  // (a block's groups dealt over a wave count no kernel here has)
+      if (sweep_kernel(*sw, src.bits != nullptr) == SWEEP_NONE) return false;  // (a block's groups dealt over a wave count no kernel here has)
       // a SPARSE message vector (ACTIVE_ONLY programs; round 6): k_spmv_sell_sparse -- single-shard structures, 16 waves, not under the static presence bits of a dense x
       // (large graphs only -- the sweep walks all its slices however few columns are present: unchanged SSSP.cpp RMAT-22 6.5 -> 12.3 ms and
       // RMAT-23 11.5 -> 14.4 ms when it was taken there, 21.6 -> 20.0 ms at RMAT-24, 84 -> 60 ms at RMAT-26; sweep_form bit 6 lifts the size
       // limit for tests, bit 5 refuses the form)
-      if (xb != nullptr && ((acc & dev::ACC_STATIC_BITS) || (opt.sweep_form & SF_NO_SPARSE) || (Aout.nnz < 200000000ll && !(opt.sweep_form & SF_SPARSE_ANY_SIZE)))) return false;
+      if (src.bits != nullptr && ((acc & dev::ACC_STATIC_BITS) || (opt.sweep_form & SF_NO_SPARSE) || (Aout.nnz < 200000000ll && !(opt.sweep_form & SF_SPARSE_ANY_SIZE)))) return false;
       if (Aout.vals != nullptr && !(sw->val_bytes == 4 && sizeof(E) == 4 && std::is_trivially_copyable<E>::value)) return false;
       return true;
     } else {
-      (void)acc; (void)sw;
+      (void)acc; (void)src; (void)sw;
       return false;
     }
   }
@@ -1472,11 +1524,11 @@ class Run {
   // (k_short_fold's fused form is instantiated for such vertex properties only)
   static constexpr bool kFoldApplyTypes = std::is_trivially_copyable<V>::value && sizeof(V) <= 16;
 
-  // The schedule of this multiply (acc, sw, defer_join: multiply_out_swept's).  Asks the graph for the two products streams: a stream it
+  // The schedule of this multiply (acc, sw, may_fold_apply, defer_join: multiply_out_swept's).  Asks the graph for the two products streams: a stream it
   // cannot give leaves its rows to their own kernels.
-  SweptSchedule swept_schedule(int acc, const gm_sweep_t& sw, bool defer_join) {
+  SweptSchedule swept_schedule(int acc, const gm_sweep_t& sw, bool may_fold_apply, bool defer_join) {
     SweptSchedule sc{};
-    const bool sparse_x = xb != nullptr;
+    const bool sparse_x = msg.bits != nullptr;
     // Giant rows.  Their fold passes read a products stream (gm_csr_t.gterm_off); when the reduction has such a two-pass form
     // (float sums: the exact replay; plain ordered folds) the SWEEP gathers for them -- slice by slice, with its LDS hot sets,
     // a slice's giant edges dealt evenly over the workgroups -- and only the fold passes remain, on the auxiliary stream next to
@@ -1496,7 +1548,7 @@ class Run {
     }
     // (a graph with few busy rows and a column-blocked stream of its short rows, graphmat_hip.h: gm_blocked_t: the stream instead of the
     // row-blocks, on the main stream -- it wants the whole chip, like the sweep)
-    const bool shorts_blocked = blocked_usable(acc, &sc.bl);
+    const bool shorts_blocked = blocked_usable(acc, msg, &sc.bl);
     // The 768-thread form (gm_sweep_t.waves = 12; experiment of round 6): the sweep leaves every CU a quarter of its registers and 36 KB of LDS,
     // and EVERYTHING else runs beside it on the auxiliary stream from the moment x is complete: the giant rows' gathers in slice order
     // (k_giant_gather_sliced), their fold passes, then the short rows' kernel.  (Not in front of the column-blocked stream or a deferred
@@ -1549,8 +1601,8 @@ class Run {
     // rows again from x).  The rows that are neither short nor without in-edges are applied by step_pull behind the join (fold_rest_mask).
     if constexpr (kFoldApplyTypes) {
       const bool giants_off_x = sc.giants == GIANTS_NONE || (sc.giants == GIANTS_SWEEP_GATHERS && opt.giant_maps != 0 && Aout.gchunk_state != nullptr);
-      sc.fold_applies = sc.shorts == SHORTS_FOLDED && fold_apply_want && !(opt.sweep_form & SF_NO_FOLD_APPLY) && sw.nsub <= 1 && !multi && !defer_join &&
-                        (acc & dev::ACC_STATIC_BITS) && giants_off_x && !rk_unverified && d_want == nullptr && xq == (const T*)x;
+      sc.fold_applies = sc.shorts == SHORTS_FOLDED && may_fold_apply && !(opt.sweep_form & SF_NO_FOLD_APPLY) && sw.nsub <= 1 && !multi && !defer_join &&
+                        (acc & dev::ACC_STATIC_BITS) && giants_off_x && !rk_unverified && d_want == nullptr && msg.x == (const T*)x;
     }
     return sc;
   }
@@ -1562,7 +1614,7 @@ class Run {
       with_edge_values<E>(Aout.vals != nullptr && sw.gval != nullptr, [&](auto hv) {
         constexpr bool HV = decltype(hv)::value;
         hipLaunchKernelGGL((dev::k_giant_gather_sliced<P, T, U, V, E, HV>), dim3(2048), dim3(dev::kBlock), 0, aux.s, pa, sw.gcol, HV ? sw.gval : (const uint32_t*)nullptr, sw.gdst,
-                           (int64_t)sw.ngiant_edges, xq, sc.gterms);
+                           (int64_t)sw.ngiant_edges, msg.x, sc.gterms);
       });
       st.spmv_launches++;
     }
@@ -1570,7 +1622,7 @@ class Run {
     Ag.nblk = 0; Ag.nmid = 0; Ag.nmid_long = 0;
     Launch Lg = launch_ctx();
     Lg.terms_ready = sc.gterms != nullptr;
-    launch_spmv_vp<P, T, U, V, E>(use_vp, Lg, pa, Ag, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+    launch_spmv_vp<P, T, U, V, E>(use_vp, Lg, pa, Ag, msg.x, msg.bits, (const V*)d_vp, y, ybits, acc, rk);
   }
   // the short rows' row-block pass, on the main stream or (SHORTS_BESIDE) on the auxiliary stream, which the join then waits for
   void swept_short_rows(const dev::ProgArg<P>& pa, int acc, bool on_aux) {
@@ -1581,18 +1633,18 @@ class Run {
     La.aux = nullptr;
     La.tiled_untiled_pass = true;
     if (on_aux) { La.s = aux.s; La.timer = nullptr; }
-    launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, As, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+    launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, As, msg.x, msg.bits, (const V*)d_vp, y, ybits, acc, rk);
     if (on_aux) { GM_HIP_OK(hipEventRecord(aux.join, aux.s)); aux.pending = true; }
   }
   // SHORTS_FOLDED: the short rows' fold from the products the sweep left (next to the giant rows' fold passes on the auxiliary stream)
-  void swept_short_fold(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, const SweptSchedule& sc) {
+  // returns whether the fold applied its rows and sent for them
+  bool swept_short_fold(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, const SweptSchedule& sc) {
     bool fused_fold = false;
     if constexpr (kFoldApplyTypes) {
       if (sc.fold_applies && fold_rest_mask(sw) != nullptr) {
         hipLaunchKernelGGL((dev::k_short_fold<P, U, T, V, true>), dim3((unsigned)sw.nbins), dim3(512), 0, s, pa, (const U*)sc.sterms, sw.sinv, sw.schunk, sw.nslices, sw.bin_cap,
                            sw.sbin_row, sw.soff, sw.srow, y, (uint32_t*)nullptr, d_vp, x, desc.row_lo);
         fused_fold = true;
-        fold_applied = true;
         fold_applies++;
         if (verbose && !said_fold_apply) { printf("GraphMat(HIP):   the fold applies its rows and sends their next messages (k_short_fold, fused; no pass over y for them)\n"); said_fold_apply = true; }
       }
@@ -1604,6 +1656,7 @@ class Run {
     short_folds++;
     if (verbose && !said_short_fold) { printf("GraphMat(HIP):   the rows of up to %d edges ride the sweep (k_short_fold)\n", (int)sw.short_row); said_short_fold = true; }
     timer.mark(TAG_ROWBLOCK);  // (the short rows' share of the multiply that is not inside the sweep)
+    return fused_fold;
   }
   // launch `set` of the sweep: the kernel's leading arguments are the same in every form, and all but the sparse form gather for the giant rows
   // (gt: their products stream, in the launch that does)
@@ -1618,7 +1671,7 @@ class Run {
         hipLaunchKernelGGL(k, dim3(256), dim3(threads), 0, s, pa, set, sc.stage, sw.nslices, sw.nrows_long, sw.slice_base, sw.scol, sval, rows, sw.row_of_slot, sw.lcol, lval, sw.lps,
                            sw.lrow_of_slot, tail...);
       };
-      auto launch_giants = [&](auto k, unsigned threads, const uint32_t* rows, auto... tail) { launch(k, threads, rows, sw.gcol, gval, sw.gdst, sw.gslice, gt, xq, y, tail...); };
+      auto launch_giants = [&](auto k, unsigned threads, const uint32_t* rows, auto... tail) { launch(k, threads, rows, sw.gcol, gval, sw.gdst, sw.gslice, gt, msg.x, y, tail...); };
       switch (kernel) {
         case SWEEP_SHARDED:  // a shard's rows: the message vector is made of nsub owners' ranges
           launch_giants(&dev::k_spmv_sell_sharded<P, T, U, V, E, HV>, 1024, stores ? sw.wrow_stream : sw.wrow, sw.nsub, sw.stride, sw.hot_words, stores ? sc.sterms : (U*)nullptr);
@@ -1626,7 +1679,7 @@ class Run {
         case SWEEP_SPARSE:  // a sparse message vector: presence tests per entry, y's presence bits OR-ed in
           if (verbose && !said_sparse_sweep) { printf("GraphMat(HIP):   sparse message vector through the sweep (k_spmv_sell_sparse)\n"); said_sparse_sweep = true; }
           if (set == 0) sparse_sweeps++;
-          launch(&dev::k_spmv_sell_sparse<P, T, U, V, E, HV>, 1024, sw.wrow, xq, xb, y, ybits);
+          launch(&dev::k_spmv_sell_sparse<P, T, U, V, E, HV>, 1024, sw.wrow, msg.x, msg.bits, y, ybits);
           break;
         case SWEEP_W12:  // 768-thread workgroups
           launch_giants(&dev::k_spmv_sell_w12<P, T, U, V, E, HV>, 768, sw.wrow);
@@ -1644,9 +1697,12 @@ class Run {
   // of a probed strategy.
   // defer_join: return without waiting for the auxiliary stream (the giant rows' fold passes): the caller joins (aux.wait_join) before it
   // touches the giant rows' y entries -- the sharded swept schedule applies, sends and starts exchanging all other rows meanwhile
-  void multiply_out_swept(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, bool defer_join = false) {
+  // may_fold_apply: the caller would apply and send behind this multiply (PullPlan.fold_may_apply), so the short rows' fold may do both for its
+  // rows; returns whether it did -- the caller then applies the other rows only (fold_rest_mask)
+  bool multiply_out_swept(const dev::ProgArg<P>& pa, int acc, const gm_sweep_t& sw, bool may_fold_apply, bool defer_join = false) {
+    bool fold_sent = false;
     if constexpr (sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<T>::value && std::is_trivially_copyable<U>::value) {
-      const SweptSchedule sc = swept_schedule(acc, sw, defer_join);
+      const SweptSchedule sc = swept_schedule(acc, sw, may_fold_apply, defer_join);
       auto fork = [&]() {
         GM_HIP_OK(hipEventRecord(aux.fork, s));
         GM_HIP_OK(hipStreamWaitEvent(aux.s, aux.fork, 0));
@@ -1665,7 +1721,7 @@ class Run {
         swept_giant_rows(pa, acc, sw, sc);
       }
       if (sc.shorts == SHORTS_BEHIND) swept_short_rows(pa, acc, false);
-      if (sc.shorts == SHORTS_FOLDED) swept_short_fold(pa, acc, sw, sc);
+      if (sc.shorts == SHORTS_FOLDED) fold_sent = swept_short_fold(pa, acc, sw, sc);
       if (aux.pending && !defer_join) GM_HIP_OK(hipStreamWaitEvent(s, aux.join, 0));
       aux.keep = aux.forked = aux.pending = false;
       timer.mark(defer_join ? TAG_ROWBLOCK : TAG_GIANT);  // (the multiply ends when the auxiliary stream has joined: the wait is charged to the giant rows' passes)
@@ -1674,10 +1730,11 @@ class Run {
         st.spmv_launches += 1;
         timer.mark(TAG_ROWBLOCK);
       }
-      if (!defer_join) check_probed(pa, Aout, xb != nullptr ? (const uint32_t*)ybits : Aout.rowbits, nullptr, acc, ybits, xb == nullptr);
+      if (!defer_join) msg = check_probed(pa, Aout, msg.bits != nullptr ? (const uint32_t*)ybits : Aout.rowbits, nullptr, acc, ybits, msg);
     } else {
-      (void)pa; (void)acc; (void)sw; (void)defer_join;
+      (void)pa; (void)acc; (void)sw; (void)may_fold_apply; (void)defer_join;
     }
+    return fold_sent;
   }
 
   // ---- schedule: the fixed-count loop of a SHARDED ALL_VERTICES run whose rows the sweep takes (round 6) ------------------------------
@@ -1691,15 +1748,13 @@ class Run {
   // place and the entries are scattered over them.  Every row is folded by the same kernels in the same order as in the plain loop: same
   // bits.  Needs what the two-stage schedule needs (a second message buffer; a program that leaves do_every_iteration to the base class)
   // plus the sparse exchange; DBG_NO_PIPELINE (128) keeps the plain loop.
-  bool swept_pipeline_applies(gm_sweep_t* sw) {
+  bool swept_pipeline_applies(gm_sweep_t* sw) const {
     if constexpr (kSparseT && sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<U>::value) {
       if (!(multi && act == ALL_VERTICES && order == OUT_EDGES && iterations > 1 && !(opt.debug_flags & dev::DBG_NO_PIPELINE) && !trace && inherits_iteration_hook<P>())) return false;
       if (!(gm_graph_exchange_caps(g) & GM_XCAP_SPARSE) || rk_unverified || opt.fuse_apply_send == 0) return false;
-      xq = x;
-      xb = nullptr;
       // (everything above is the same on every shard; what follows is not -- a shard may hold no swept row -- and the shards must take the
       // same schedule, or their collectives do not match: MIN over the shards of "fine here")
-      int fine = (sweep_usable(dev::ACC_STATIC_BITS, sw) && sw->nsub > 1 && Aout.ngiant <= dev::kSparseListCap && n_live >= 64) ? 1 : 0;
+      int fine = (sweep_usable(dev::ACC_STATIC_BITS, XSource{x, nullptr}, sw) && sw->nsub > 1 && Aout.ngiant <= dev::kSparseListCap && n_live >= 64) ? 1 : 0;
       gm_graph_exchange(g, GM_XCHG_CONVERGED, nullptr, 0, nullptr, &fine);
       return fine == 1;
     } else {
@@ -1743,26 +1798,17 @@ class Run {
       if (verbose) printf("GraphMat(HIP): sharded swept schedule: %d giant rows here, blocks of %d entries; the all-gather travels while they fold\n", Aout.ngiant, cap);
       T* xcur = x;
       T* xnext = x2v;
-      const int ag = grid_for(n_live) < dev::kApplyMaxBlocks ? grid_for(n_live) : dev::kApplyMaxBlocks;
       int it = 0;
-      {
-        dev::ProgArg<P> pa = dev::make_prog_arg(gp);
-        timer.mark(TAG_START);
-        send_all(pa, nullptr, xcur);
-        if (gm_graph_exchange(g, GM_XCHG_MESSAGES, xcur, (int64_t)sizeof(T), xbits, nullptr) != 0) die("message exchange callback failed");
-        timer.mark(TAG_SEND);
-      }
+      sharded_first_messages(xcur);
       for (; it < iterations; it++) {
         dev::ProgArg<P> pa = dev::make_prog_arg(gp);
         const bool more = it + 1 < iterations;
         timer.mark(TAG_START);
-        xq = xcur;
-        xb = nullptr;
-        multiply_out_swept(pa, dev::ACC_STATIC_BITS, sw, more);
+        msg = XSource{xcur, nullptr};
+        multiply_out_swept(pa, dev::ACC_STATIC_BITS, sw, false, more);
         if (more) {
           // every row but the giant ones: apply, the next message, and off they go
-          hipLaunchKernelGGL((dev::k_apply_send<P, T, U, V>), dim3(ag), dim3(dev::kBlock), 0, s, pa, (const U*)y, (const uint32_t*)bits_rest, d_vp, d_active, n_live, d_changed,
-                             (uint32_t*)nullptr, xnext, xbits, desc.row_lo);
+          apply_rows(pa, APPLY_SEND, 0, n_live, bits_rest, dev::kApplyMaxBlocks, nullptr, xnext);
           timer.mark(TAG_APPLY);
           int part[2] = {0, n_live};
           if (gm_graph_exchange(g, GM_XCHG_PART, xnext, (int64_t)sizeof(T), nullptr, part) != 0) die("partial message exchange failed");
@@ -1780,16 +1826,12 @@ class Run {
           hipLaunchKernelGGL((dev::k_unpack_frontier<T>), dim3(grid_for(nall)), dim3(dev::kBlock), 0, s, (const xentry_t*)gather, nall, xnext, xbits);
           timer.mark(TAG_SEND);
         } else {
-          hipLaunchKernelGGL((dev::k_apply<P, U, V, false>), dim3(ag), dim3(dev::kBlock), 0, s, pa, (const U*)y, Aout.rowbits, d_vp, d_active, n_live, d_changed,
-                             (const int64_t*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (unsigned int*)nullptr);
+          apply_rows(pa, APPLY_PLAIN, 0, n_live, Aout.rowbits, dev::kApplyMaxBlocks, nullptr, xnext);
           timer.mark(TAG_APPLY);
         }
         if (n_live < n && it == 0) GM_HIP_OK(hipMemsetAsync(d_active + n_live / 32, 0, (size_t)(nwords - n_live / 32) * 4, s));
-        gp->do_every_iteration(it);  // (the base class's empty hook: this schedule is only taken by programs that do not override it)
-        T* t = xcur; xcur = xnext; xnext = t;
+        sharded_end_iteration(it, xcur, xnext);
       }
-      fill_active();
-      finish(it);
       return it;
     } else {
       (void)sw;
@@ -1797,33 +1839,22 @@ class Run {
     }
   }
 
-  // Can this run's pull multiply of the OUT adjacency take the column-blocked stream of the short rows (graphmat_hip.h: gm_blocked_t;
-  // kernels.hpp: k_spmv_blocked)?  The conditions of the sweep; the structure exists only for graphs without skew (edge values: none, or 4 bytes in its entries).
-  bool said_blocked = false, said_sparse_sweep = false, said_short_fold = false;
+  bool said_blocked = false, said_sparse_sweep = false, said_short_fold = false, said_fold_apply = false;
   int sparse_sweeps = 0;  // multiplies of this run that took a sparse x through the sweep (note GM_NOTE_SPARSE_SWEEPS of the graph: tests read it)
   int short_folds = 0;    // multiplies of this run whose short rows were folded from the sweep's products stream (GM_NOTE_SHORT_FOLDS)
-  // fold + apply + send (kernels.hpp: k_short_fold, FUSED): step_pull says before a multiply that today's path would run k_apply_send behind it
-  // (fold_apply_want); multiply_out_swept answers whether its fold applied the short rows and sent for them (fold_applied)
-  bool fold_apply_want = false, fold_applied = false, said_fold_apply = false;
-  int fold_applies = 0;   // multiplies of this run whose fold also applied and sent (GM_NOTE_FOLD_APPLIES)
-  // which step every iteration of run_loop took (graphmat_hip.h: notes GM_NOTE_STEP_COUNTS and GM_NOTE_STEP_KINDS of the graph: tests compare them with the rule restated on the host)
-  enum { STEP_PULL = 0, STEP_LIST = 1, STEP_BITS = 2, STEP_DENSE_PUSH = 3 };
-  unsigned int step_count[4] = {0, 0, 0, 0};  // iterations per kind, saturating at 65535
-  unsigned long long step_kinds = 0;          // the kinds of the first 32 iterations, two bits each
-  void count_step(int it, int kind) {
-    if (step_count[kind] < 0xffffu) step_count[kind]++;
-    if (it < 32) step_kinds |= (unsigned long long)kind << (2 * it);
-  }
-  bool blocked_usable(int acc, gm_blocked_t* bl) {
+  int fold_applies = 0;   // multiplies of this run whose fold also applied and sent (kernels.hpp: k_short_fold, FUSED; GM_NOTE_FOLD_APPLIES)
+  // Can this run's pull multiply of the OUT adjacency take the column-blocked stream of the short rows (graphmat_hip.h: gm_blocked_t;
+  // kernels.hpp: k_spmv_blocked)?  The conditions of the sweep; the structure exists only for graphs without skew (edge values: none, or 4 bytes in its entries).
+  bool blocked_usable(int acc, XSource src, gm_blocked_t* bl) const {
     if constexpr (sizeof(T) == 4 && sizeof(U) == 4 && std::is_trivially_copyable<T>::value && std::is_trivially_copyable<U>::value) {
-      if (use_vp || xq == nullptr || xb != nullptr || d_want != nullptr || program_row_filter<P>::enabled || (acc & dev::ACC_READ_PREV)) return false;
+      if (use_vp || src.x == nullptr || src.bits != nullptr || d_want != nullptr || program_row_filter<P>::enabled || (acc & dev::ACC_READ_PREV)) return false;
       if (!(rk == REDUCE_ORDERED || rk == REDUCE_F32_ADD || rk == REDUCE_COMMUTATIVE)) return false;
       if (opt.debug_flags & dev::DBG_NO_TILES) return false;
       if (gm_graph_blocked(g, bl) != GM_OK || bl->nrows <= 0 || bl->short_row != Aout.short_row) return false;
       if (Aout.vals != nullptr && !(bl->val_bytes == 4 && bl->eval != nullptr && sizeof(E) == 4 && std::is_trivially_copyable<E>::value)) return false;
       return true;
     } else {
-      (void)acc; (void)bl;
+      (void)acc; (void)src; (void)bl;
       return false;
     }
   }
@@ -1865,7 +1896,7 @@ class Run {
         constexpr bool HV = decltype(vals_c)::value;
         constexpr int UBV = decltype(ub_c)::value;
         hipLaunchKernelGGL((dev::k_spmv_blocked<P, T, U, V, E, HV, UBV>), dim3(256), dim3(1024), GM_BLOCKED_ROWS * 4, s, pa, bl.ecol, bl.erow, bl.eval, bl.woff, bl.nslices, bl.nblocks,
-                           bl.row_of, xq, y, bl.step_count, bl.nsteps, window);
+                           bl.row_of, msg.x, y, bl.step_count, bl.nsteps, window);
       };
       const bool ub4 = (opt.blocked_form & 16) != 0;
       with_edge_values<E>(Aout.vals != nullptr, [&](auto vals_c) {
@@ -1884,12 +1915,12 @@ class Run {
       if (Ar.nmid > 0 || Ar.ngiant > 0) {
         Launch La = launch_ctx();
         La.aux = nullptr;  // (few rows, if any: everything on the run's stream)
-        launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, Ar, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+        launch_spmv_vp<P, T, U, V, E>(use_vp, La, pa, Ar, msg.x, msg.bits, (const V*)d_vp, y, ybits, acc, rk);
       }
       launch_blocked(pa, bl);
       st.spmv_launches += 1;
       timer.mark(TAG_ROWBLOCK);
-      check_probed(pa, Aout, Aout.rowbits, nullptr, acc, ybits, true);
+      msg = check_probed(pa, Aout, Aout.rowbits, nullptr, acc, ybits, msg);
     } else {
       (void)pa; (void)acc; (void)bl;
     }
@@ -1925,14 +1956,14 @@ class Run {
     if (Aout.tile_min_row == 0) { As.nblk = 0; As.nmid = 0; }  // every row is tiled
     // (running the untiled pass on a stream of its own next to the tile passes -- its rows are no tile's rows -- was measured:
     // 7.06 -> 7.03 ms at RMAT-26, not worth a third stream)
-    launch_spmv_vp<P, T, U, V, E>(use_vp, L, pa, As, xq, xb, (const V*)d_vp, y, ybits, acc, rk);
+    launch_spmv_vp<P, T, U, V, E>(use_vp, L, pa, As, msg.x, msg.bits, (const V*)d_vp, y, ybits, acc, rk);
     aux.long_rows = !(opt.debug_flags & dev::DBG_LONG_ON_MAIN);
     for (int t = 0; t < ntile; t++) {
       gm_csr_t At;
       const uint32_t* prev = nullptr;
       if (gm_graph_tile(g, GM_DIR_OUT, t, &At, &prev) != GM_OK) die(gm_last_error());
       // y's presence bits are static (dense x): `prev` says which rows already carry a value
-      launch_spmv_vp<P, T, U, V, E>(use_vp, L, pa, At, xq, xb, (const V*)d_vp, y, const_cast<uint32_t*>(prev), dev::ACC_STATIC_BITS | dev::ACC_READ_PREV, rk);
+      launch_spmv_vp<P, T, U, V, E>(use_vp, L, pa, At, msg.x, msg.bits, (const V*)d_vp, y, const_cast<uint32_t*>(prev), dev::ACC_STATIC_BITS | dev::ACC_READ_PREV, rk);
     }
     aux.long_rows = false;
     if (aux.keep) {
@@ -1941,7 +1972,7 @@ class Run {
     }
     // (a probed strategy is cross-checked against the ordered fold of the WHOLE rows; a mismatch redoes this iteration
     // untiled with the ordered fold, which then also governs the tiled iterations that follow)
-    check_probed(pa, Aout, Aout.rowbits, nullptr, acc, ybits, true);
+    msg = check_probed(pa, Aout, Aout.rowbits, nullptr, acc, ybits, msg);
   }
 
   // top-down step over a larger active set inside the pull step: bids, then one pass over all vertices picks the winners
@@ -1952,146 +1983,226 @@ class Run {
     hipLaunchKernelGGL(dev::k_push_bid, dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, Asrc, (const int32_t*)d_list, (int)frontier_v,
                        (const unsigned int*)d_off, native_of_dev, d_best, (const uint32_t*)d_want, (int32_t*)nullptr, (unsigned int*)nullptr);
     with_flag(use_vp, [&](auto vp_c) {
-      hipLaunchKernelGGL((dev::k_push_resolve<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid_for(n_live)), dim3(dev::kBlock), 0, s, pa, Asrc, xq, dev_of_native,
+      hipLaunchKernelGGL((dev::k_push_resolve<P, T, U, V, E, decltype(vp_c)::value>), dim3(grid_for(n_live)), dim3(dev::kBlock), 0, s, pa, Asrc, msg.x, dev_of_native,
                          (const V*)d_vp, d_best, y, ybits, n_live);  // (only live rows can have been bid for)
     });
     st.spmv_launches += 2;
     timer.mark(TAG_WAVE);
   }
 
-  void step_pull(const dev::ProgArg<P>& pa, int it, bool xsp, bool dense_push, bool want_stats) {
-    // Clear(&x) / Clear(&y) (:139-140): x presence words are fully rewritten by send.  With every x entry present
-    // (ALL_VERTICES) y's presence is the static set of non-empty rows.
-    const bool static_bits = (act == ALL_VERTICES);
-    const bool dense_x = (act == ALL_VERTICES);
-    if (!static_bits) GM_HIP_OK(hipMemsetAsync(ybits, 0, (size_t)nwords * 4, s));
+  // What one pull step does, decided by plan_pull before the step's first launch; step_pull launches it.
+  enum SendKind {      // how this iteration's messages get into x
+    SEND_SPARSE,       // the sparse exchange: the listed active vertices' messages as (device id, message) entries (send_sparse)
+    SEND_LAZY,         // not at all: the multiply evaluates them on demand from the senders' properties (lazy_send)
+    SEND_PRESENT,      // they are there: the fused apply pass of the iteration before wrote them (x_presend)
+    SEND_ALL           // k_send over the live rows
+  };
+  enum GuidedKind {    // guided pull: only the rows that an active vertex reaches are folded
+    GUIDED_OFF,
+    GUIDED_LIST,       // rows marked from the list of the active vertices, a workgroup per 1024 out-edges (a hub is spread over the chip)
+    GUIDED_BITMAP      // rows marked from the active bitmap (more active vertices than the list holds)
+  };
+  enum OutPath {       // the multiply of the OUT adjacency
+    OUT_NONE,          // an IN_EDGES program
+    OUT_DENSE_PUSH,    // top-down: bids from the listed active set, one pass over all vertices picks the winners (multiply_dense_push)
+    OUT_SWEPT,         // multiply_out_swept
+    OUT_BLOCKED,       // multiply_out_blocked
+    OUT_TILED,         // multiply_out_tiled
+    OUT_CSR            // the whole-graph CSR's kernels (launch_spmv)
+  };
+  struct PullPlan {
+    bool want_stats;            // run_loop's: apply sizes (and lists) the next active set
+    bool dense_x;               // every x entry present (ALL_VERTICES); y's presence is then the static set of non-empty rows
+    SendKind send;
+    XSource src;                // what the multiply reads messages from
+    GuidedKind guided;
+    bool guided_few;            // so few out-edges that the kernel working through a wave's wanted rows one after the other pays
+    const uint32_t* row_bits;   // which rows the OUT multiply works on: the marked ones, the program's row filter, or null = all
+    uint32_t* xsum;             // the 64:1 summary of x's presence words (GM_WS_XSUM) for the short-row kernel of an a=b program, when wanted and obtained
+    int xwords, nsum;           // ... the presence words it summarises and its own
+    OutPath out;
+    int acc_out;                // the OUT multiply's ACC_* flags
+    gm_sweep_t sw;              // OUT_SWEPT: the structure
+    gm_blocked_t bl;            // OUT_BLOCKED: the stream
+    int ntile;                  // OUT_TILED: the column tiles
+    bool in_pass;               // the IN adjacency is multiplied (behind the OUT pass of an ALL_EDGES program)
+    int acc_in;                 // ... its ACC_* flags
+    uint32_t* in_ybits;         // ... y's presence words as it reads and writes them (a dense x: the OUT pass's static ones, only read)
+    const uint32_t* apply_bits; // the presence words apply reads
+    bool fuse_next;             // another iteration follows for certain and nothing can change what send_message reads before it: apply may send its messages
+    bool fold_may_apply;        // ... and so may the short rows' fold of a swept multiply
+    bool build_list;            // apply lists the changed vertices
+    int apply_cap;              // apply's largest grid
+  };
+
+  // Launches nothing; looks the graph's structures up and asks for the summary's workspace (a table look-up after the first iteration).
+  PullPlan plan_pull(int it, const StepChoice& step, bool want_stats) {
+    PullPlan pl{};
+    const bool xsp = step.xsp, dense_push = step.kind == STEP_DENSE_PUSH;
+    pl.want_stats = want_stats;
+    pl.dense_x = act == ALL_VERTICES;
+    pl.send = xsp ? SEND_SPARSE : lazy_send ? SEND_LAZY : x_presend ? SEND_PRESENT : SEND_ALL;
+    pl.src.x = lazy_send ? (const T*)nullptr : (const T*)x;
+    pl.src.bits = pl.dense_x ? nullptr : (lazy_send ? (const uint32_t*)d_active : (const uint32_t*)xbits);
+    // few out-edges leave the active set: mark the rows they reach, fold only those (same kernels, same order)
+    pl.guided = !(guided && !dense_push && !xsp && frontier_v > 0 && frontier_e * 50ull < (unsigned long long)Aout.nnz) ? GUIDED_OFF
+                : frontier_v <= (unsigned long long)dev::kSparseListCap                                                    ? GUIDED_LIST
+                                                                                                                            : GUIDED_BITMAP;
+    pl.row_bits = pl.guided != GUIDED_OFF ? d_mark : d_want;
+    // (the kernel that takes 64 list entries per wave and works on the wanted ones one after the other pays for a handful of wanted rows;
+    // with thousands of them the 16-rows-per-wave kernels, which skip unwanted rows as well, are several times faster: RMAT-26 BFS level
+    // with 857 K out-edges 14.3 ms against ~4)
+    pl.guided_few = pl.guided == GUIDED_OFF || frontier_e <= 4096ull;
+    const int acc_static = pl.dense_x ? dev::ACC_STATIC_BITS : 0;
+    if (dense_push) {
+      pl.out = OUT_DENSE_PUSH;
+    } else if (order == OUT_EDGES || order == ALL_EDGES) {
+      pl.acc_out = acc_static;
+      // sparse active set of an a=b program: a 64:1 summary of the presence bits for the short-row kernel
+      const unsigned long long present_x = xsparse_ok ? (unsigned long long)xs_total : frontier_v;  // entries of x that are present
+      if (want_stats && rk == REDUCE_LAST && pl.src.bits != nullptr && present_x * 512ull < (unsigned long long)n_live * (unsigned long long)desc.nshards) {
+        void* ps = nullptr;
+        pl.xwords = (desc.ndevice + 31) / 32;  // x (and its presence bits) cover every shard's rows
+        pl.nsum = (pl.xwords / 2 + 31) / 32 + 1;
+        if (gm_graph_workspace(g, GM_WS_XSUM, (size_t)pl.nsum * 4 + 64, &ps) == GM_OK) pl.xsum = (uint32_t*)ps;
+      }
+      pl.ntile = 1;
+      if (pl.dense_x && !multi && pl.row_bits == nullptr && rk != REDUCE_LAST && dev::stageable<T>::value && !(opt.debug_flags & dev::DBG_NO_TILES))
+        gm_graph_tiles(g, GM_DIR_OUT, &pl.ntile);
+      // (the sweep takes sharded graphs too: gm_sweep_t.nsub; and a sparse x: k_spmv_sell_sparse)
+      pl.out = pl.row_bits == nullptr && !xsp && sweep_usable(pl.acc_out, pl.src, &pl.sw)                    ? OUT_SWEPT
+               : pl.dense_x && !multi && pl.row_bits == nullptr && blocked_usable(pl.acc_out, pl.src, &pl.bl) ? OUT_BLOCKED
+               : pl.ntile > 1                                                                                 ? OUT_TILED
+                                                                                                              : OUT_CSR;
+    }
+    pl.in_pass = !dense_push && (order == IN_EDGES || order == ALL_EDGES);
+    if (pl.in_pass) {
+      pl.acc_in = (order == ALL_EDGES ? dev::ACC_READ_PREV : 0) | acc_static;
+      pl.in_ybits = pl.dense_x ? const_cast<uint32_t*>(Aout.rowbits) : ybits;
+    }
+    // apply reads y's own presence words, or -- static -- those of the rows with an edge in a direction the program multiplies
+    if (!pl.dense_x) pl.apply_bits = ybits;
+    else if (order == OUT_EDGES) pl.apply_bits = Aout.rowbits;
+    else if (order == IN_EDGES) pl.apply_bits = Ain.rowbits;
+    else if (gm_graph_rowbits_all(g, &pl.apply_bits) != GM_OK) die(gm_last_error());
+    // Another iteration follows: its messages can come out of the apply pass.  Only for programs without a do_every_iteration
+    // of their own (nothing can change what send_message reads between the two iterations), and only in fixed-count
+    // runs: until convergence the last iteration is not known in advance, and a fused pass there would leave x holding
+    // messages of an iteration that never runs (the reference's px would not)
+    pl.fuse_next = inherits_iteration_hook<P>() && pl.dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations;
+    pl.fold_may_apply = pl.fuse_next && !want_stats && order == OUT_EDGES && !dense_push && !xsp;
+    // The changed vertices are listed when the next active set is bound to be small: it cannot have more vertices than the
+    // current one has out-edges.  (If it turns out small without having been listed, a k_frontier_list pass builds the list
+    // when it is needed.)
+    pl.build_list = want_stats && frontier_e <= (4ull << 20);
+    // (a workgroup that lists changed vertices ends with one global atomic: fewer, longer-running workgroups then)
+    pl.apply_cap = pl.build_list ? dev::kApplyMaxBlocks / 4 : dev::kApplyMaxBlocks;
+    return pl;
+  }
+  // the apply pass behind the step's multiplies, from the plan and the one fact only the multiply knows: whether its fold applied the short rows
+  static ApplyKind apply_kind(const PullPlan& pl, bool fold_sent) {
+    return pl.want_stats ? APPLY_STATS : fold_sent ? APPLY_SEND_MASKED : pl.fuse_next ? APPLY_SEND : APPLY_PLAIN;
+  }
+
+  // guided pull: d_mark = the rows that an out-edge of an active vertex reaches
+  void mark_guided_rows(GuidedKind kind) {
+    GM_HIP_OK(hipMemsetAsync(d_mark, 0, ((size_t)(n + 31) / 32 + 2) * 4, s));
+    if (kind == GUIDED_LIST) {
+      list_active_set();
+      const int nf = (int)frontier_v;
+      const unsigned pieces = (unsigned)(frontier_e / dev::kPieceEdges + frontier_v);
+      piece_offsets(nf);
+      hipLaunchKernelGGL(dev::k_mark_rows_of_list, dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, Asrc, (const int32_t*)d_list, nf, (const unsigned int*)d_off, d_mark);
+    } else {
+      const int mgrid = grid_for(n_live) < 4096 ? grid_for(n_live) : 4096;
+      hipLaunchKernelGGL(dev::k_mark_rows_of_active, dim3(mgrid), dim3(dev::kBlock), 0, s, Asrc, (const uint32_t*)d_active, n_live, d_mark);
+    }
+    if (verbose) printf("GraphMat(HIP):   guided pull: %llu active vertices, %llu out-edges\n", frontier_v, frontier_e);
+  }
+  // the 64:1 summary of x's presence words
+  void summarise_presence(const PullPlan& pl) {
+    hipLaunchKernelGGL(dev::k_bits_summary, dim3(grid_for(pl.nsum)), dim3(dev::kBlock), 0, s, pl.src.bits, pl.xwords, pl.xsum, pl.nsum);
+  }
+
+  void step_pull(const dev::ProgArg<P>& pa, int it, const StepChoice& step, bool want_stats) {
+    const PullPlan pl = plan_pull(it, step, want_stats);
+    msg = pl.src;
+    // Clear(&x) / Clear(&y) (:139-140): x presence words are fully rewritten by send; y's are static with a dense x
+    if (!pl.dense_x) GM_HIP_OK(hipMemsetAsync(ybits, 0, (size_t)nwords * 4, s));
     // send (:145).  Rows past n_live have no edge in either direction (degree-ranked order puts them at the tail): nobody
     // reads their messages and they never receive one
-    if (xsp) {
+    x_presend = false;  // (SEND_PRESENT consumes it; only ever set for programs that cannot change between the iterations)
+    if (pl.send == SEND_SPARSE) {
       send_sparse(pa);
     } else {
-      const bool presend_valid = x_presend;  // (only ever set for programs that cannot change between the iterations)
-      x_presend = false;
-      if (!lazy_send && !presend_valid) send_all(pa, dense_x ? (const uint32_t*)nullptr : (const uint32_t*)d_active, x);
+      if (pl.send == SEND_ALL) send_all(pa, pl.dense_x ? (const uint32_t*)nullptr : (const uint32_t*)d_active, x);
       if (multi && gm_graph_exchange(g, GM_XCHG_MESSAGES, x, (int64_t)sizeof(T), xbits, nullptr) != 0) die("message exchange callback failed");
     }
     timer.mark(TAG_SEND);
     lap("Send message time");
     // multiply + reduce (:160-176)
-    xq = lazy_send ? (const T*)nullptr : (const T*)x;
-    xb = dense_x ? nullptr : (lazy_send ? (const uint32_t*)d_active : (const uint32_t*)xbits);
-    const uint32_t* apply_bits = ybits;
-    const uint32_t* row_bits = d_want;  // which rows the multiply works on
-    bool guided_few = true;
-    if (guided && !dense_push && !xsp && frontier_v > 0 && frontier_e * 50ull < (unsigned long long)Aout.nnz) {
-      // few out-edges leave the active set: mark the rows they reach, fold only those (same kernels, same order)
-      GM_HIP_OK(hipMemsetAsync(d_mark, 0, ((size_t)(n + 31) / 32 + 2) * 4, s));
-      if (frontier_v <= (unsigned long long)dev::kSparseListCap) {  // few vertices: from their list, a workgroup per 1024 out-edges (a hub is spread over the chip)
-        list_active_set();
-        const int nf = (int)frontier_v;
-        const unsigned pieces = (unsigned)(frontier_e / dev::kPieceEdges + frontier_v);
-        piece_offsets(nf);
-        hipLaunchKernelGGL(dev::k_mark_rows_of_list, dim3(pieces > 0 ? pieces : 1), dim3(dev::kBlock), 0, s, Asrc, (const int32_t*)d_list, nf, (const unsigned int*)d_off, d_mark);
-      } else {
-        const int mgrid = grid_for(n_live) < 4096 ? grid_for(n_live) : 4096;
-        hipLaunchKernelGGL(dev::k_mark_rows_of_active, dim3(mgrid), dim3(dev::kBlock), 0, s, Asrc, (const uint32_t*)d_active, n_live, d_mark);
-      }
-      row_bits = d_mark;
-      // (the kernel that takes 64 list entries per wave and works on the wanted ones one after the other pays for a handful of wanted rows;
-      // with thousands of them the 16-rows-per-wave kernels, which skip unwanted rows as well, are several times faster: RMAT-26 BFS level
-      // with 857 K out-edges 14.3 ms against ~4)
-      guided_few = frontier_e <= 4096ull;
-      if (verbose) printf("GraphMat(HIP):   guided pull: %llu active vertices, %llu out-edges\n", frontier_v, frontier_e);
+    if (pl.guided != GUIDED_OFF) mark_guided_rows(pl.guided);
+    if (pl.xsum != nullptr) summarise_presence(pl);
+    bool fold_sent = false;  // the short rows' fold of a swept multiply applied them and sent for them
+    switch (pl.out) {
+      case OUT_DENSE_PUSH: multiply_dense_push(pa); break;
+      case OUT_SWEPT: fold_sent = multiply_out_swept(pa, pl.acc_out, pl.sw, pl.fold_may_apply); break;
+      case OUT_BLOCKED: multiply_out_blocked(pa, pl.acc_out, pl.bl); break;
+      case OUT_TILED: multiply_out_tiled(pa, pl.ntile, pl.acc_out); break;
+      case OUT_CSR:
+        launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, Aout, msg.x, msg.bits, (const V*)d_vp, y, ybits, pl.acc_out, rk, pl.row_bits, grouped_waves && pl.guided_few,
+                                      (const uint32_t*)pl.xsum);
+        msg = check_probed(pa, Aout, pl.dense_x ? Aout.rowbits : (const uint32_t*)ybits, pl.row_bits, pl.acc_out, ybits, msg);
+        break;
+      case OUT_NONE: break;
     }
-    // would k_apply_send run behind this multiply (the test below)?  Then the short rows' fold may apply and send (multiply_out_swept)
-    fold_applied = false;
-    fold_apply_want = !want_stats && inherits_iteration_hook<P>() && dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations &&
-                      order == OUT_EDGES && !dense_push && !xsp;
-    if (dense_push) {
-      multiply_dense_push(pa);
-    } else if (order == OUT_EDGES || order == ALL_EDGES) {
-      const int acc = static_bits ? dev::ACC_STATIC_BITS : 0;
-      // sparse active set of an a=b program: a 64:1 summary of the presence bits for the short-row kernel
-      const uint32_t* xsum = nullptr;
-      const unsigned long long present_x = xsparse_ok ? (unsigned long long)xs_total : frontier_v;  // entries of x that are present
-      if (want_stats && rk == REDUCE_LAST && xb != nullptr && present_x * 512ull < (unsigned long long)n_live * (unsigned long long)desc.nshards) {
-        void* ps = nullptr;
-        const int xwords = (desc.ndevice + 31) / 32;  // x (and its presence bits) cover every shard's rows
-        const int nsum = (xwords / 2 + 31) / 32 + 1;
-        if (gm_graph_workspace(g, GM_WS_XSUM, (size_t)nsum * 4 + 64, &ps) == GM_OK) {
-          hipLaunchKernelGGL(dev::k_bits_summary, dim3(grid_for(nsum)), dim3(dev::kBlock), 0, s, xb, xwords, (uint32_t*)ps, nsum);
-          xsum = (const uint32_t*)ps;
-        }
-      }
-      int ntile = 1;
-      if (dense_x && !multi && row_bits == nullptr && rk != REDUCE_LAST && dev::stageable<T>::value && !(opt.debug_flags & dev::DBG_NO_TILES))
-        gm_graph_tiles(g, GM_DIR_OUT, &ntile);
-      gm_sweep_t sw;
-      gm_blocked_t bl;
-      if (row_bits == nullptr && !xsp && sweep_usable(acc, &sw)) {  // (sharded graphs too: gm_sweep_t.nsub; a sparse x too: k_spmv_sell_sparse)
-        multiply_out_swept(pa, acc, sw);
-      } else if (dense_x && !multi && row_bits == nullptr && blocked_usable(acc, &bl)) {
-        multiply_out_blocked(pa, acc, bl);
-      } else if (ntile > 1) {
-        multiply_out_tiled(pa, ntile, acc);
-      } else {
-        launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, Aout, xq, xb, (const V*)d_vp, y, ybits, acc, rk, row_bits, grouped_waves && guided_few, xsum);
-        check_probed(pa, Aout, static_bits ? Aout.rowbits : (const uint32_t*)ybits, row_bits, acc, ybits, dense_x);
-      }
-      if (static_bits) apply_bits = Aout.rowbits;
-    }
-    if (!dense_push && (order == IN_EDGES || order == ALL_EDGES)) {
-      int acc = (order == ALL_EDGES) ? dev::ACC_READ_PREV : 0;
-      uint32_t* yb = ybits;
-      if (static_bits) {
-        acc |= dev::ACC_STATIC_BITS;
-        yb = const_cast<uint32_t*>(Aout.rowbits);  // only read (presence of the OUT pass's results)
-        apply_bits = Ain.rowbits;
-        if (order == ALL_EDGES && gm_graph_rowbits_all(g, &apply_bits) != GM_OK) die(gm_last_error());
-      }
-      launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, Ain, (const T*)x, xb, (const V*)d_vp, y, yb, acc, rk, (const uint32_t*)d_want, grouped_waves);
-      if (order == IN_EDGES) check_probed(pa, Ain, static_bits ? Ain.rowbits : (const uint32_t*)ybits, d_want, acc, ybits, dense_x);
+    if (pl.in_pass) {
+      launch_spmv_vp<P, T, U, V, E>(use_vp, launch_ctx(), pa, Ain, (const T*)x, msg.bits, (const V*)d_vp, y, pl.in_ybits, pl.acc_in, rk, (const uint32_t*)d_want, grouped_waves);
+      if (order == IN_EDGES) msg = check_probed(pa, Ain, pl.dense_x ? Ain.rowbits : (const uint32_t*)ybits, d_want, pl.acc_in, ybits, msg);
     }
     lap("SPMV time");
-    if (trace) tr_updated = count_bits(apply_bits, n_live);  // y.getNNZ(): rows that received a message
+    if (trace) tr_updated = count_bits(pl.apply_bits, n_live);  // y.getNNZ(): rows that received a message
     // setAllInactive (:184) + apply (:195-225): the active vector is rewritten by k_apply (when top-down steps are
-    // possible the kernel also sizes and lists the next active set).  The changed vertices are also listed when the next
-    // active set is bound to be small: it cannot have more vertices than the current one has out-edges.  (If it turns
-    // out small without having been listed, a k_frontier_list pass builds the list when it is needed.)
-    const bool build_list = want_stats && frontier_e <= (4ull << 20);
+    // possible the kernel also sizes and lists the next active set)
     if (want_stats) GM_HIP_OK(hipMemsetAsync(d_count, 0, 4, s));
-    listed = build_list;
-    // (a workgroup that lists changed vertices ends with one global atomic: fewer, longer-running workgroups then)
-    const int apply_cap = build_list ? dev::kApplyMaxBlocks / 4 : dev::kApplyMaxBlocks;
-    const int apply_grid = grid_for(n_live) < apply_cap ? grid_for(n_live) : apply_cap;
-    if (want_stats)
-      hipLaunchKernelGGL((dev::k_apply<P, U, V, true>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, apply_bits, d_vp, d_active, n_live,
-                         d_changed, Asrc.rowptr, d_striped, d_want, build_list ? d_list : (int32_t*)nullptr, build_list ? d_count : (unsigned int*)nullptr);
-    else if (fold_applied) {
-      // the fold applied the short rows and wrote their next messages: what remains are the sweep's and the giant rows (fold_rest_mask); rows
-      // without in-edges keep their property and the message of the run's first send.  The active vector, the changed flag and x's presence
-      // words are not touched: a fixed-count run reads none of them before its last iteration, whose plain k_apply rewrites the first two for
-      // every row (the presence words are all set since the first send)
-      gm_sweep_t swm;
-      gm_graph_sweep(g, &swm);
-      hipLaunchKernelGGL((dev::k_apply_send_masked<P, T, U, V>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, fold_rest_mask(swm), d_vp, n_live, x, desc.row_lo);
-      x_presend = true;
-    } else if (inherits_iteration_hook<P>() && dense_x && !lazy_send && !trace && opt.fuse_apply_send != 0 && iterations > 0 && it + 1 < iterations) {
-      // another iteration follows: its messages come out of the same pass.  Only for programs without a do_every_iteration
-      // of their own (nothing can change what send_message reads between the two iterations), and only in fixed-count
-      // runs: until convergence the last iteration is not known in advance, and a fused pass there would leave x holding
-      // messages of an iteration that never runs (the reference's px would not)
-      hipLaunchKernelGGL((dev::k_apply_send<P, T, U, V>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, apply_bits, d_vp, d_active, n_live,
-                         d_changed, d_want, x, xbits, desc.row_lo);
-      x_presend = true;
-    } else
-      hipLaunchKernelGGL((dev::k_apply<P, U, V, false>), dim3(apply_grid), dim3(dev::kBlock), 0, s, pa, (const U*)y, apply_bits, d_vp, d_active, n_live,
-                         d_changed, (const int64_t*)nullptr, (unsigned long long*)nullptr, d_want, (int32_t*)nullptr, (unsigned int*)nullptr);
+    listed = pl.build_list;
+    const ApplyKind kind = apply_kind(pl, fold_sent);
+    // (behind a fold that applied and sent: what remains are the sweep's and the giant rows, fold_rest_mask; rows without in-edges keep their
+    // property and the message of the run's first send.  The masked pass touches neither the active vector nor the changed flag nor x's presence
+    // words: a fixed-count run reads none of them before its last iteration, whose plain k_apply rewrites the first two for every row, and the
+    // presence words are all set since the first send)
+    apply_rows(pa, kind, 0, n_live, kind == APPLY_SEND_MASKED ? fold_rest_mask(pl.sw) : pl.apply_bits, pl.apply_cap, d_want, x, pl.build_list);
+    x_presend = kind == APPLY_SEND_MASKED || kind == APPLY_SEND;
     if (n_live < n && it == 0)  // setAllInactive for the rows k_apply does not visit (they have no edges: once clear, nothing sets them again)
       GM_HIP_OK(hipMemsetAsync(d_active + n_live / 32, 0, (size_t)(nwords - n_live / 32) * 4, s));
-    fold_apply_want = false;
     timer.mark(TAG_APPLY);
     lap("Apply time");
+  }
+
+  // which step every iteration of run_loop took (graphmat_hip.h: notes GM_NOTE_STEP_COUNTS and GM_NOTE_STEP_KINDS of the graph: tests compare them with the rule restated on the host)
+  unsigned int step_count[4] = {0, 0, 0, 0};  // iterations per kind, saturating at 65535
+  unsigned long long step_kinds = 0;          // the kinds of the first 32 iterations, two bits each
+  void count_step(int it, int kind) {
+    if (step_count[kind] < 0xffffu) step_count[kind]++;
+    if (it < 32) step_kinds |= (unsigned long long)kind << (2 * it);
+  }
+  // The step of the coming iteration, from the size of its active set (frontier_*: vertices, their out-edges, the largest out-degree)
+  StepChoice choose_step() const {
+    StepChoice c{};
+    // this iteration's x travels as lists when every shard's active set is small: fewer bytes than the dense slices
+    // (entry = id + message against one message per live row) and within the list capacity
+    c.xsp = xsparse_ok && xs_max <= dev::kSparseListCap && (unsigned long long)xs_max * sizeof(xentry_t) * 2ull < (unsigned long long)n_live * sizeof(T);
+    // top-down step for small active sets only: few sources and few out-edges
+    const bool push = can_push && frontier_v > 0 && frontier_v <= (unsigned long long)dev::kSparseListCap &&
+                      frontier_e * 1000ull < (unsigned long long)Aout.nnz * (unsigned long long)opt.push_edge_permille;
+    // ... and among those, active sets with few out-edges run entirely on lists (nothing scans all vertices)
+    const bool sparse = push && frontier_e <= (unsigned long long)opt.sparse_step_edges;
+    const bool dense_push = push && !sparse && rk == REDUCE_LAST;
+    // ... and an active set too large to list whose vertices own only a few out-edges each bids straight from the bitmap
+    const bool bits_push = can_push && !push && rk == REDUCE_LAST && frontier_v > (unsigned long long)dev::kSparseListCap &&
+                           frontier_e <= (unsigned long long)opt.bits_step_edges && frontier_maxdeg <= 64ull;
+    c.kind = bits_push ? STEP_BITS : sparse ? STEP_LIST : dense_push ? STEP_DENSE_PUSH : STEP_PULL;
+    return c;
   }
 
   // ---- the loop (GraphMatRuntime.h:136-261) ----------------------------------------------------------------------------
@@ -2109,28 +2220,15 @@ class Run {
       // a fixed-count run never reads the flag (:254-256), so it is not cleared either: one tiny fill kernel less per iteration
       if (iterations <= 0) GM_HIP_OK(hipMemsetAsync(d_changed, 0, want_stats ? sizeof(int) + striped_bytes : sizeof(int), s));
       timer.mark(TAG_START);
-      // this iteration's x travels as lists when every shard's active set is small: fewer bytes than the dense slices
-      // (entry = id + message against one message per live row) and within the list capacity
-      const bool xsp = xsparse_ok && xs_max <= dev::kSparseListCap &&
-                       (unsigned long long)xs_max * sizeof(xentry_t) * 2ull < (unsigned long long)n_live * sizeof(T);
-      // top-down step for small active sets only: few sources and few out-edges
-      const bool push = can_push && frontier_v > 0 && frontier_v <= (unsigned long long)dev::kSparseListCap &&
-                        frontier_e * 1000ull < (unsigned long long)Aout.nnz * (unsigned long long)opt.push_edge_permille;
-      // ... and among those, active sets with few out-edges run entirely on lists (nothing scans all vertices)
-      const bool sparse = push && frontier_e <= (unsigned long long)opt.sparse_step_edges;
-      const bool dense_push = push && !sparse && rk == REDUCE_LAST;
-      // ... and an active set too large to list whose vertices own only a few out-edges each bids straight from the bitmap
-      const bool bits_push = can_push && !push && rk == REDUCE_LAST && frontier_v > (unsigned long long)dev::kSparseListCap &&
-                             frontier_e <= (unsigned long long)opt.bits_step_edges && frontier_maxdeg <= 64ull;
-      const int step_kind = bits_push ? STEP_BITS : sparse ? STEP_LIST : dense_push ? STEP_DENSE_PUSH : STEP_PULL;
-      count_step(it, step_kind);
+      const StepChoice step = choose_step();
+      count_step(it, step.kind);
       if (verbose && can_push) {
         static const char* const step_names[4] = {"pull", "list push", "bits push", "pull with dense push"};
-        printf("GraphMat(HIP):   step: %s\n", step_names[step_kind]);
+        printf("GraphMat(HIP):   step: %s\n", step_names[step.kind]);
       }
-      if (bits_push) step_bits_push(pa);
-      else if (sparse) step_list_push(pa);
-      else step_pull(pa, it, xsp, dense_push, want_stats);
+      if (step.kind == STEP_BITS) step_bits_push(pa);
+      else if (step.kind == STEP_LIST) step_list_push(pa);
+      else step_pull(pa, it, step, want_stats);
 
       int converged = 0;
       if (iterations <= 0) {  // the flag only matters when running until convergence (:257-259)

@@ -201,6 +201,37 @@ def test_untraited_programs_on_a_graph_with_giant_rows(tmp_path):
 
 
 @pytest.mark.gpu
+def test_guided_pull_marks_rows_from_the_active_bitmap(tmp_path):
+    """apps/untraited_programs.cpp with guided_pull = 2 on a star: vertex 1 -> 70000 middle vertices, the first 1000 of which -> one leaf
+    each.  Level 0 owns nearly every edge (a plain pull); level 1 has more active vertices than a list holds (65536) and 1000 out-edges, so
+    its rows are marked from the active BITMAP (k_mark_rows_of_active); level 2, the leaves, from the list.  BFS depths and parents and
+    SSSP distances of every reached vertex against the oracle, and the verbose lines of both marked levels."""
+    from graphmat_amd.mtx import write_mtx_bin
+    from oracle import binding as ob
+    ob.build()
+    exe = _need(os.path.join(OWN_APPS, "untraited_programs"))
+    width, tails = 70000, 1000
+    mid = np.arange(2, 2 + width, dtype=np.int32)
+    s = np.concatenate([np.full(width, 1, np.int32), mid[:tails]])
+    d = np.concatenate([mid, mid[:tails] + width])
+    nv = 1 + width + tails
+    v = (1 + (np.arange(s.size, dtype=np.int64) * 7919) % 97).astype(np.int32)
+    path = str(tmp_path / "star.bin.mtx")
+    write_mtx_bin(path, nv, s, d, v)
+    text = _run(exe, path, 1, 1, env={"GRAPHMAT_NUM_THREADS": "1", "GRAPHMAT_OPTIONS": "guided_pull=2", "GRAPHMAT_VERBOSE": "1"})
+    assert text.count("   guided pull: %d active vertices, %d out-edges" % (width, tails)) == 2, text[:2000]  # BFS and SSSP, from the bitmap
+    assert text.count("   guided pull: %d active vertices, 0 out-edges" % tails) == 2  # ... and from the list
+    og = ob.OracleGraph(nv, s, d, v, ref_threads=1)
+    od, op, _, _ = og.bfs(1)
+    assert (od != 0xFFFFFFFF).all()
+    got = {int(a): (int(b), int(c)) for a, b, c in re.findall(r"^bfs (\d+) (\d+) (-?\d+)$", text, flags=re.M)}
+    assert got == {i + 1: (int(od[i]), -1 if i == 0 else int(op[i])) for i in range(nv)}
+    odist, _ = og.sssp(1)
+    gots = {int(a): int(b) for a, b in re.findall(r"^sssp (\d+) (\d+)$", text, flags=re.M)}
+    assert gots == {i + 1: int(odist[i]) for i in range(nv)}
+
+
+@pytest.mark.gpu
 def test_cpp_surface_selftest():
     """apps/api_selftest.cpp: Graph<V,E> get/set, getEdgelist, applyToAll*, activity, a (mul,add)
     SpMV and chain BFS through include/*.h -- the reference's unit tests re-expressed."""

@@ -5,12 +5,14 @@
 
 Each file is split at its function symbols; per symbol, the text from `.type SYM,@function` to `.size SYM` -- the instructions and,
 for a kernel, its .amdhsa_kernel block -- is compared.  The order of the functions in the file follows the order of instantiation and
-may differ; so may the function's index inside local labels (.LBB12_3, .Lfunc_end12), which is masked, and the lines that carry
-the per-compile `__hip_cuid_<hash>` symbol.  Reads assembly for equality only.  Exit status 0 = same symbols, same bodies."""
+may differ; so may the function's index inside local labels (.LBB12_3, .Lfunc_end12) and inside the comments that name a block
+(`in Loop: Header=BB12_2`, `Child Loop BB12_27`), which is masked (with the padding in front of a comment, which follows the label's length), and the lines that carry the per-compile
+`__hip_cuid_<hash>` symbol.  Reads assembly for equality only.  Exit status 0 = same symbols, same bodies."""
 import re
 import sys
 
-LOCAL = re.compile(r"(\.L[A-Za-z_]+?)\d+(_\d+)?\b")
+LOCAL = re.compile(r"(\.L[A-Za-z_]+?|\bBB)\d+(_\d+)?\b")
+PAD = re.compile(r"[ \t]+;")
 TYPE = re.compile(r"^\s*\.type\s+(\S+),@function")
 SIZE = re.compile(r"^\s*\.size\s+(\S+),")
 
@@ -31,7 +33,7 @@ def functions(path):
                 out[sym] = "".join(body)
                 sym = None
             else:
-                body.append(LOCAL.sub(lambda k: k.group(1) + (k.group(2) or ""), line))
+                body.append(PAD.sub(" ;", LOCAL.sub(lambda k: k.group(1) + (k.group(2) or ""), line)))
     return out
 
 
