@@ -335,6 +335,16 @@ class Graph:
         check(self.L.gm_run_connected_components(self.h, t.data_ptr(), C.byref(n), _stream()))
         return int(n.value), self.to_vertex_order(t).cpu().numpy()
 
+    # ---- k-core decomposition ----------------------------------------------------------------
+    def core_numbers(self):
+        """gm_run_kcore: (kmax, core int32[nv] in vertex order, index v-1).  core[v-1] = the core number of v in the simple
+        undirected graph under the edge list (directions ignored, self-loops dropped, duplicates and antiparallel pairs
+        counted once): what networkx.core_number returns; a vertex without neighbours has 0."""
+        t = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        kmax = C.c_int32(0)
+        check(self.L.gm_run_kcore(self.h, t.data_ptr(), C.byref(kmax), _stream()))
+        return int(kmax.value), self.to_vertex_order(t).cpu().numpy()
+
 
 _hip = None
 

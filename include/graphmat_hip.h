@@ -643,6 +643,20 @@ int gm_run_triangle_count(gm_graph_t* g, int64_t* d_triangles, uint64_t* h_total
  * *h_ncomponents (may be NULL) = the number of components.  The call returns after the stream has finished. */
 int gm_run_connected_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncomponents, gm_stream_t stream);
 
+/* K-core decomposition by peeling (gm_kcore.hip): the simple undirected adjacency is built from ONE adjacency of the graph
+ * (GM_DIR_OUT when the graph has it, else GM_DIR_IN: every build gives the same numbers) into workspace, once per call; then, level
+ * by level, the alive vertices of the smallest degree k are listed and peeled in passes: a listed vertex gets core number k and
+ * takes one off each alive neighbour's degree, and a neighbour that comes down to k joins the next pass.  Levels jump over the
+ * values of k that nobody has.  Whole (unsharded) graphs; edge values and column tiles are ignored.  gm_graph_last_stats
+ * afterwards: send_ms = the adjacency build, spmv_ms = the peel, apply_ms = the finish, iterations = peel passes,
+ * spmv_launches = levels (= distinct core numbers). */
+/* Core numbers of the simple undirected graph under the edge list (what networkx.core_number returns): edge directions are
+ * ignored, self-loops dropped, duplicate edges and a pair u -> v, v -> u count once.  core[v] = the largest k such that v lies
+ * in a subgraph whose vertices all have at least k neighbours; a vertex without neighbours has 0.
+ * d_core: int32 [nrows] in device order, overwritten; unused device slots (native_of_dev == -1) get 0.
+ * *h_kmax (may be NULL) = the largest core number (the degeneracy; 0 without edges).  The call returns after the stream has finished. */
+int gm_run_kcore(gm_graph_t* g, int32_t* d_core, int32_t* h_kmax, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -796,9 +810,18 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *                            vertex id per root
  *  21   GM_WS_CC_FLAG        connected components: the last round   64                                 gm_components.hip                     no
  *                            that found work, the component count
+ *  19   GM_WS_KC_ADJ         k-core: rowptr and entries of the      (n + 1) * 8 + nnz * 20 + 320       gm_kcore.hip                          no
+ *                            simple undirected adjacency (at most
+ *                            2 * nnz), then each edge's row and
+ *                            its two places while it is built
+ *  20   GM_WS_KC_STATE       k-core: degrees and both frontier      n * 12 + nnz / 128 + n / 256 + 72K gm_kcore.hip                          no
+ *                            lists, then the long rows of a pass
+ *                            and the scan's block sums
+ *  21   GM_WS_KC_FLAG        k-core: k, list lengths, alive count,  64                                 gm_kcore.hip                          no
+ *                            kmax
  *
- * Slots 19-21: gm_run_triangle_count and gm_run_connected_components are separate calls, neither runs inside the other, and
- * neither keeps anything in these slots from one call to the next (each writes everything it reads there, every call), so
+ * Slots 19-21: gm_run_triangle_count, gm_run_connected_components and gm_run_kcore are separate calls, none runs inside another,
+ * and none keeps anything in these slots from one call to the next (each writes everything it reads there, every call), so
  * their uses never live in one run; like all runs on one graph, the calls follow each other on one stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
  * exact commutative ones of at most 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
@@ -835,6 +858,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_CC_EDGE_ROWS 19
 #define GM_WS_CC_MIN 20
 #define GM_WS_CC_FLAG 21
+#define GM_WS_KC_ADJ 19
+#define GM_WS_KC_STATE 20
+#define GM_WS_KC_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
