@@ -335,6 +335,15 @@ class Graph:
         check(self.L.gm_run_connected_components(self.h, t.data_ptr(), C.byref(n), _stream()))
         return int(n.value), self.to_vertex_order(t).cpu().numpy()
 
+    def strong_components(self):
+        """gm_run_strong_components: (ncomponents, labels int32[nv] in vertex order, index v-1).  labels[v-1] = the smallest
+        vertex id of v's strongly connected component (directions matter, duplicates and self-loops do not); a vertex
+        without edges, or with a self-loop only, is its own component.  The graph must hold both adjacencies."""
+        t = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        n = C.c_int32(0)
+        check(self.L.gm_run_strong_components(self.h, t.data_ptr(), C.byref(n), _stream()))
+        return int(n.value), self.to_vertex_order(t).cpu().numpy()
+
     # ---- k-core decomposition ----------------------------------------------------------------
     def core_numbers(self):
         """gm_run_kcore: (kmax, core int32[nv] in vertex order, index v-1).  core[v-1] = the core number of v in the simple

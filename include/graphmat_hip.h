@@ -657,6 +657,25 @@ int gm_run_connected_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_nco
  * *h_kmax (may be NULL) = the largest core number (the degeneracy; 0 without edges).  The call returns after the stream has finished. */
 int gm_run_kcore(gm_graph_t* g, int32_t* d_core, int32_t* h_kmax, gm_stream_t stream);
 
+/* Strongly connected components by trimming and colouring (gm_scc.hip).  First every vertex without alive in-neighbours or without
+ * alive out-neighbours is taken away as a component of its own, in passes over frontier lists, until none is left (the trim).
+ * Then rounds, while vertices remain: every alive vertex's colour starts as its own vertex id and passes over the edges lower it
+ * to the smallest id among its alive ancestors; a vertex that keeps its own id is a root, and passes against the edges mark what
+ * reaches a root within its colour: that is the root's component.  The marked vertices are removed and the trim runs again.
+ * BOTH adjacencies are walked (in- and out-neighbours of single vertices): a graph built with only one of GM_DIR_OUT / GM_DIR_IN is
+ * refused (GM_ERR_UNSUPPORTED; no transpose is built inside the call), as are shards, row ranges and graphs with an exchange
+ * callback.  Edge values and column tiles are ignored.  At most n rounds and n + 1 passes a phase; the passes grow with the
+ * longest chain the trim peels and with the longest shortest path inside a component (a directed cycle of L vertices takes about L
+ * forward and L backward passes), and each pass is a launch and a 32-byte read.  gm_graph_last_stats afterwards: iterations =
+ * rounds, spmv_launches = passes (trim lists processed, forward and backward passes with the confirming ones; not the removal
+ * pass of a round); send_ms = set-up and the first trim, spmv_ms = the rounds with their trims, apply_ms = what remains.
+ * Edge directions matter, duplicate edges and self-loops do not.
+ * labels[v] = the smallest 1-based VERTEX id in v's strongly connected component (the convention of
+ * gm_run_connected_components).  A vertex without edges, or with a self-loop only, is its own component.
+ * d_labels: int32 [nrows] in device order, overwritten; unused device slots (native_of_dev == -1) get 0.
+ * *h_ncomponents (may be NULL) = the number of distinct labels.  The call returns after the stream has finished. */
+int gm_run_strong_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncomponents, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -819,10 +838,21 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *                            and the scan's block sums
  *  21   GM_WS_KC_FLAG        k-core: k, list lengths, alive count,  64                                 gm_kcore.hip                          no
  *                            kmax
+ *  19   GM_WS_SCC_EDGES      strong components: the row of every    nnz * 12 + 256                     gm_scc.hip                            no
+ *                            OUT edge, then both ends of the edges
+ *                            alive after the first trim
+ *  20   GM_WS_SCC_STATE      strong components: in- and out-degree  n * 28 + nnz / 64 + 592            gm_scc.hip                            no
+ *                            counters, vertex ids, states, colours,
+ *                            both lists, the long rows of a pass
+ *  21   GM_WS_SCC_FLAG       strong components: list lengths, long  64                                 gm_scc.hip                            no
+ *                            rows handed over, the last pass that
+ *                            changed something, roots, kept edges,
+ *                            used slots
  *
- * Slots 19-21: gm_run_triangle_count, gm_run_connected_components and gm_run_kcore are separate calls, none runs inside another,
- * and none keeps anything in these slots from one call to the next (each writes everything it reads there, every call), so
- * their uses never live in one run; like all runs on one graph, the calls follow each other on one stream.
+ * Slots 19-21: gm_run_triangle_count, gm_run_connected_components, gm_run_kcore and gm_run_strong_components are four separate
+ * calls, none runs inside another, and none keeps anything in these slots from one call to the next (each writes everything it
+ * reads there, every call), so their uses never live in one run; like all runs on one graph, the calls follow each other on one
+ * stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
  * exact commutative ones of at most 4 bytes; their pull steps fold giant rows block-wide (reductions of at most 8 bytes) or with
  * one wave per row (larger ones, which no products stream can hold) and never ask for GM_WS_GIANT_TERMS: that is the
@@ -861,6 +891,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_KC_ADJ 19
 #define GM_WS_KC_STATE 20
 #define GM_WS_KC_FLAG 21
+#define GM_WS_SCC_EDGES 19
+#define GM_WS_SCC_STATE 20
+#define GM_WS_SCC_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
