@@ -344,6 +344,39 @@ class Graph:
         check(self.L.gm_run_strong_components(self.h, t.data_ptr(), C.byref(n), _stream()))
         return int(n.value), self.to_vertex_order(t).cpu().numpy()
 
+    # ---- betweenness centrality --------------------------------------------------------------
+    def _betweenness(self, sources, last):
+        bc = torch.zeros(self.rows, dtype=torch.float64, device=self.device)
+        depth = torch.zeros(self.rows, dtype=torch.int32, device=self.device) if last else None
+        sigma = torch.zeros(self.rows, dtype=torch.float64, device=self.device) if last else None
+        if sources is None:
+            ptr, n = None, 0
+        else:
+            src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)  # (alive until the call has returned)
+            ptr, n = src.ctypes.data, int(src.size)
+            if n == 0:
+                src = np.zeros(1, np.int32)  # an empty list is not "all vertices": a valid pointer, no entries
+                ptr = src.ctypes.data
+        check(self.L.gm_run_betweenness(self.h, ptr, n, bc.data_ptr(), depth.data_ptr() if last else None,
+                                        sigma.data_ptr() if last else None, _stream()))
+        return bc, depth, sigma
+
+    def betweenness(self, sources=None):
+        """gm_run_betweenness: float64 [nv] in vertex order, index v-1.  Brandes' betweenness centrality of the simple directed
+        graph under the edge list (duplicates count once, self-loops and edge values are ignored), unnormalised, endpoints not
+        counted, summed over `sources` (1-based vertex ids; a source listed twice counts twice; None = every vertex, which is
+        networkx.betweenness_centrality(DiGraph, normalized=False)).  For a symmetric edge list the values are twice
+        networkx's undirected ones.  The graph must hold the GM_DIR_IN adjacency."""
+        bc, _, _ = self._betweenness(sources, False)
+        return self.to_vertex_order(bc).cpu().numpy()
+
+    def shortest_path_counts(self, source):
+        """gm_run_betweenness with one source and its two optional outputs: (depth int32[nv], sigma float64[nv]) in vertex
+        order.  depth = the BFS level (-1 = not reached), sigma = the number of shortest paths from `source` (0 where not
+        reached; a double: exact below 2^53)."""
+        _, depth, sigma = self._betweenness([int(source)], True)
+        return self.to_vertex_order(depth).cpu().numpy(), self.to_vertex_order(sigma).cpu().numpy()
+
     # ---- k-core decomposition ----------------------------------------------------------------
     def core_numbers(self):
         """gm_run_kcore: (kmax, core int32[nv] in vertex order, index v-1).  core[v-1] = the core number of v in the simple

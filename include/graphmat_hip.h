@@ -676,6 +676,34 @@ int gm_run_kcore(gm_graph_t* g, int32_t* d_core, int32_t* h_kmax, gm_stream_t st
  * *h_ncomponents (may be NULL) = the number of distinct labels.  The call returns after the stream has finished. */
 int gm_run_strong_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncomponents, gm_stream_t stream);
 
+/* Betweenness centrality after Brandes (2001), level by level (gm_betweenness.hip): unweighted, DIRECTED, unnormalised, endpoints
+ * not counted, on the simple directed graph under the edge list (duplicate edges count once, self-loops and edge values are
+ * ignored).  For the sources S:  bc[v] = sum over s in S of delta_s(v), delta_s(s) = 0, where sigma_s(w) is the number of shortest
+ * s -> w paths and delta_s(v) = sum over v -> w with depth(w) = depth(v) + 1 of sigma(v) / sigma(w) * (1 + delta_s(w)) (each term
+ * divided, then multiplied).  With S = all vertices this is networkx.betweenness_centrality(DiGraph, normalized=False), with a
+ * subset networkx.betweenness_centrality_subset(G, S, all nodes, normalized=False); a source that appears twice counts twice.
+ * For a symmetric edge list (every edge given both ways) the values are TWICE networkx's undirected ones: every unordered pair
+ * of end points is counted from both ends.  sigma, delta and bc are fp64: path counts leave int64 on graphs of many levels; while
+ * sigma < 2^53 it is an exact integer whatever the order of its sums.
+ * h_sources: HOST array of nsources 1-based vertex ids; h_sources == NULL && nsources == 0 means all vertices 1..nv.
+ * d_bc: double [nrows] in device order, overwritten; unused device slots (native_of_dev == -1) get 0.
+ * d_last_depth (int32 [nrows]) and d_last_sigma (double [nrows]) may be NULL; they receive the LAST source's depths (-1 = not
+ * reached) and path counts (0 where not reached), in device order (without any source: -1 and 0 everywhere).
+ * Per source: a forward phase over frontier lists (a look at depth[w], a compare-and-swap where it shows -1, the hardware fp64
+ * atomic add of sigma) whose lists stay, one level after the other, in one array; then a backward phase from the level before
+ * the deepest down to level 1 that PULLS: every vertex sums its own out-row's terms with a fixed lane mapping and order, no float
+ * atomics.  So two calls on one graph build return the same bytes while every sigma < 2^53.  Only the GM_DIR_IN adjacency is read
+ * (its row v, rows = sources, holds v's out-neighbours): a graph without it is refused (GM_ERR_UNSUPPORTED; no transpose is built
+ * inside the call), as are shards, row ranges and graphs with an exchange callback ("whole graphs only").  GM_ERR_INVALID: null
+ * graph or d_bc, nsources < 0, NULL h_sources with nsources > 0, an id outside 1..nv (the text names it).  Refusals happen before
+ * any GPU work and leave the outputs untouched.  Cost: a source takes about two launches per level and a 32-byte read per forward
+ * level, so graphs of many levels are slow; the sources run one after another.  gm_graph_last_stats afterwards: iterations =
+ * sources processed, spmv_launches = level passes, forward plus backward (the launches for long rows are not counted); send_ms =
+ * set-up, spmv_ms = the forward phases, apply_ms = the backward phases and the finish.  The call returns after the stream has
+ * finished. */
+int gm_run_betweenness(gm_graph_t* g, const int32_t* h_sources, int32_t nsources,
+                       double* d_bc, int32_t* d_last_depth, double* d_last_sigma, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -848,9 +876,17 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *                            rows handed over, the last pass that
  *                            changed something, roots, kept edges,
  *                            used slots
+ *  19   GM_WS_BC_ORDER       betweenness: the BFS-order array (the  n * 4 + nnz / 64 + nsources * 8    gm_betweenness.hip                    no
+ *                            levels' lists one after another), the  + 400
+ *                            long rows of a source, the sources as
+ *                            vertex ids and as device ids
+ *  20   GM_WS_BC_STATE       betweenness: sigma and delta (fp64),   n * 20 + 384                       gm_betweenness.hip                    no
+ *                            depth, of the current source
+ *  21   GM_WS_BC_FLAG        betweenness: entries of the order      64                                 gm_betweenness.hip                    no
+ *                            array and long rows so far
  *
- * Slots 19-21: gm_run_triangle_count, gm_run_connected_components, gm_run_kcore and gm_run_strong_components are four separate
- * calls, none runs inside another, and none keeps anything in these slots from one call to the next (each writes everything it
+ * Slots 19-21: gm_run_triangle_count, gm_run_connected_components, gm_run_kcore, gm_run_strong_components and gm_run_betweenness
+ * are five separate calls, none runs inside another, and none keeps anything in these slots from one call to the next (each writes everything it
  * reads there, every call), so their uses never live in one run; like all runs on one graph, the calls follow each other on one
  * stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
@@ -894,6 +930,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_SCC_EDGES 19
 #define GM_WS_SCC_STATE 20
 #define GM_WS_SCC_FLAG 21
+#define GM_WS_BC_ORDER 19
+#define GM_WS_BC_STATE 20
+#define GM_WS_BC_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
