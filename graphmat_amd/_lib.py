@@ -25,6 +25,7 @@ GM_WS_CC_EDGE_ROWS, GM_WS_CC_MIN, GM_WS_CC_FLAG = 19, 20, 21  # (second names: t
 GM_WS_KC_ADJ, GM_WS_KC_STATE, GM_WS_KC_FLAG = 19, 20, 21  # (third names: the k-core call is a separate call as well)
 GM_WS_SCC_EDGES, GM_WS_SCC_STATE, GM_WS_SCC_FLAG = 19, 20, 21  # (fourth names: strong components are a separate call as well)
 GM_WS_BC_ORDER, GM_WS_BC_STATE, GM_WS_BC_FLAG = 19, 20, 21  # (fifth names: betweenness centrality is a separate call as well)
+GM_WS_MSF_EDGE_ROWS, GM_WS_MSF_STATE, GM_WS_MSF_FLAG = 19, 20, 21  # (sixth names: the spanning forest is a separate call as well)
 GM_NOTE_TWO_STAGE_SPLIT, GM_NOTE_SGD_RING_BYTES, GM_NOTE_GIANT_GATHER_CAP, GM_NOTE_SPARSE_SWEEPS, GM_NOTE_SHORT_FOLDS = 0, 1, 2, 3, 4
 GM_NOTE_STEP_COUNTS, GM_NOTE_STEP_KINDS, GM_NOTE_FOLD_APPLIES, GM_NOTE_SGD_PATH = 5, 6, 7, 8
 GM_LAYOUT_NATIVE = 0
@@ -153,6 +154,7 @@ SIGNATURES = {
     "gm_run_kcore": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P]),
     "gm_run_strong_components": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P]),
     "gm_run_betweenness": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    "gm_run_spanning_forest": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
     "gm_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "gm_graph_engine_options": (C.c_int, [_P, C.POINTER(EngineOptions)]),
     "gm_graph_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),

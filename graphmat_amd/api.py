@@ -377,6 +377,27 @@ class Graph:
         _, depth, sigma = self._betweenness([int(source)], True)
         return self.to_vertex_order(depth).cpu().numpy(), self.to_vertex_order(sigma).cpu().numpy()
 
+    # ---- minimum spanning forest --------------------------------------------------------------
+    def spanning_forest_raw(self):
+        """gm_run_spanning_forest as it is: (nedges, total, int32 tensor [rows, 3] in device order).  The row of a slot that was
+        hooked through an edge holds that edge's (u, v, w), every other row (0, 0, 0)."""
+        t = torch.zeros((self.rows, 3), dtype=torch.int32, device=self.device)
+        n = C.c_int32(0)
+        total = C.c_int64(0)
+        check(self.L.gm_run_spanning_forest(self.h, t.data_ptr(), C.byref(n), C.byref(total), _stream()))
+        return int(n.value), int(total.value), t
+
+    def spanning_forest(self):
+        """gm_run_spanning_forest: (total, edges int32[nedges, 3]).  A minimum spanning forest of the undirected multigraph under
+        the edge list (directions ignored, self-loops ignored, parallel and antiparallel edges separate candidates); a weight is
+        the edge value as a signed int32, 1 for a graph without values.  Every row is (u, v, w) with 1-based vertex ids, u < v
+        and w the weight of an input edge between u and v; the rows are sorted by (w, u, v); total = their weights' sum."""
+        n, total, t = self.spanning_forest_raw()
+        e = t.cpu().numpy()
+        e = e[e[:, 0] > 0]
+        assert e.shape[0] == n
+        return total, np.ascontiguousarray(e[np.lexsort((e[:, 1], e[:, 0], e[:, 2]))])
+
     # ---- k-core decomposition ----------------------------------------------------------------
     def core_numbers(self):
         """gm_run_kcore: (kmax, core int32[nv] in vertex order, index v-1).  core[v-1] = the core number of v in the simple

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libgraphmat_hip.so")
-SOURCES = ["gm_core.hip", "gm_graph.hip", "gm_graph_tiles.hip", "gm_graph_sweep.hip", "gm_graph_blocked.hip", "gm_programs.hip", "gm_lda.hip", "gm_triangles.hip", "gm_components.hip", "gm_kcore.hip", "gm_scc.hip", "gm_betweenness.hip", "gm_dist.hip"]
+SOURCES = ["gm_core.hip", "gm_graph.hip", "gm_graph_tiles.hip", "gm_graph_sweep.hip", "gm_graph_blocked.hip", "gm_programs.hip", "gm_lda.hip", "gm_triangles.hip", "gm_components.hip", "gm_kcore.hip", "gm_scc.hip", "gm_betweenness.hip", "gm_spanning_forest.hip", "gm_dist.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-DGRAPHMAT_NO_MPI"]
 

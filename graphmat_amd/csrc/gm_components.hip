@@ -7,7 +7,8 @@
 // strictly decreases, ends in a root (parent[r] == r) and every walk along it is bounded.
 //   k_cc_init       parent[v] = v, vmin[v] = INT_MAX, the flags block cleared
 //   k_cc_edge_rows  once per call: row_of_edge[e] for every CSR position, so that the hook kernel reads (row, column) of an edge
-//                   coalesced with lane = edge and its balance does not depend on row lengths (a giant row is no special case)
+//                   coalesced with lane = edge and its balance does not depend on row lengths (a giant row is no special case);
+//                   it lives in gm_edge_rows.hpp, which gm_spanning_forest.hip includes as well
 //   k_cc_hook       lane = edge (u, v): ru = parent[u], rv = parent[v]; if they differ, atomicMin(&parent[max], min) and the round is
 //                   marked as one that found work (one store per wave that saw a difference)
 //   k_cc_jump       lane = vertex: parent[v] follows its chain to the root; a thread writes its own entry only
@@ -34,27 +35,16 @@
 #include <limits.h>
 #include <string.h>
 
+#include "gm_edge_rows.hpp"  // k_cc_edge_rows, cc_row_of, kCcBlock, kCcPiece, cc_grid
 #include "gm_internal.hpp"
 
 namespace gm {
-
-constexpr int kCcBlock = 256;   // (not measured: the block size of gm_triangles.hip)
-constexpr int kCcPiece = 4096;  // edges per workgroup of k_cc_edge_rows (measured: 256 / 1024 / 4096 / 16384 took 1.16 / 0.41 / 0.30 / 0.49 ms on RMAT-22)
 
 struct CcFlags {         // workspace slot GM_WS_CC_FLAG
   uint32_t found_work;   // the last hook pass (counted from 1) that saw an edge between two trees
   uint32_t ncomponents;
 };
 
-// the row that holds edge e: the r in [lo, hi) with rowptr[r] <= e < rowptr[r + 1] (given rowptr[lo] <= e < rowptr[hi])
-__device__ __forceinline__ int cc_row_of(const int64_t* __restrict__ rowptr, int lo, int hi, int64_t e) {
-  while (hi - lo > 1) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (rowptr[mid] <= e) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 __device__ __forceinline__ bool cc_used(const int32_t* __restrict__ native_of_dev, int v) { return !native_of_dev || native_of_dev[v] >= 0; }
 
 // atomicMin(&a[key], val) for the lanes with `active` (a[] only ever decreases during the launch); every lane of the wave calls it.
@@ -82,19 +72,6 @@ k_cc_init(int32_t* __restrict__ parent, int32_t* __restrict__ vmin, int n, CcFla
   if (v >= n) return;
   parent[v] = v;
   vmin[v] = INT_MAX;
-}
-
-// A workgroup's kCcPiece consecutive edges lie in few rows: the rows of its first and last edge are searched in all of rowptr
-// (the same for every lane: two chains of dependent loads, which is why a piece is more than a block's worth of edges), every
-// lane then searches between the two.
-__global__ void __launch_bounds__(kCcBlock)
-k_cc_edge_rows(gm_csr_t A, int32_t* __restrict__ row_of_edge) {
-  const int64_t first = (int64_t)blockIdx.x * kCcPiece;
-  if (first >= A.nnz) return;
-  const int64_t last = first + kCcPiece - 1 < A.nnz ? first + kCcPiece - 1 : A.nnz - 1;
-  const int rlo = cc_row_of(A.rowptr, 0, A.nrows, first);
-  const int rhi = cc_row_of(A.rowptr, rlo, A.nrows, last);
-  for (int64_t e = first + threadIdx.x; e <= last; e += kCcBlock) row_of_edge[e] = cc_row_of(A.rowptr, rlo, rhi + 1, e);
 }
 
 __global__ void __launch_bounds__(kCcBlock)
@@ -147,8 +124,6 @@ k_cc_labels(int32_t* __restrict__ labels, const int32_t* __restrict__ native_of_
   if (v >= n) return;
   labels[v] = cc_used(native_of_dev, v) ? vmin[labels[v]] : 0;
 }
-
-static inline unsigned cc_grid(int64_t n, int per_block = kCcBlock) { return (unsigned)((n + per_block - 1) / per_block); }
 
 static int run_connected_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncomponents, hipStream_t s) {
   const gm_csr_t& A = g->out.present ? g->out.view : g->in.view;  // either adjacency holds every edge once

@@ -60,6 +60,7 @@ struct CsrOwned {
 namespace gm { void warm_program_kernels(void* d_scratch256); }
 #define GM_LDA_TILE_DEFAULT 64  // option "lda_tile" (gm_lda.hip; gm_reset_options restores it)
 #define GM_TC_FORM_DEFAULT 0    // option "tc_form" (gm_triangles.hip; gm_reset_options restores it)
+#define GM_MSF_FORM_DEFAULT 0   // option "msf_form" (gm_spanning_forest.hip; gm_reset_options restores it)
 
 struct gm_graph {
   gm_graph_desc_t desc;

@@ -25,6 +25,7 @@ namespace gm {
 int g_force_ordered = 0;  // (read by gm_lda.hip as well)
 extern int g_lda_tile;
 extern int g_tc_form;
+extern int g_msf_form;
 
 // ---------------- PageRank (reference: src/PageRank.cpp:34-112) ----------------------------
 struct PRv : gm_pr_t {
@@ -798,6 +799,7 @@ int gm_reset_options(void) {
   gm::g_sgd_mfma = 0;
   gm::g_lda_tile = GM_LDA_TILE_DEFAULT;
   gm::g_tc_form = GM_TC_FORM_DEFAULT;
+  gm::g_msf_form = GM_MSF_FORM_DEFAULT;
   gm::g_short_row = GM_SHORT_ROW;
   gm::g_giant_row = 0;
   gm::g_rank_cap = 0;
@@ -830,6 +832,7 @@ int gm_set_option(const char* key, int value) {
   if (key && !strcmp(key, "sgd_mfma") && (value == 0 || value == 1)) { gm::g_sgd_mfma = value; return GM_OK; }
   if (key && !strcmp(key, "lda_tile") && (value == 16 || value == 32 || value == 64)) { gm::g_lda_tile = value; return GM_OK; }
   if (key && !strcmp(key, "tc_form") && value >= 0 && value <= 2) { gm::g_tc_form = value; return GM_OK; }
+  if (key && !strcmp(key, "msf_form") && value >= 0 && value <= 11) { gm::g_msf_form = value; return GM_OK; }
   if (key && !strcmp(key, "short_row") && value >= 1 && value <= GM_BLOCK_NNZ) { gm::g_short_row = value; return GM_OK; }
   if (key && !strcmp(key, "giant_row") && value >= 64) { gm::g_giant_row = value; return GM_OK; }
   if (key && !strcmp(key, "rank_cap") && value >= 0) { gm::g_rank_cap = value; return GM_OK; }

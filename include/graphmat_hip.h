@@ -704,6 +704,27 @@ int gm_run_strong_components(gm_graph_t* g, int32_t* d_labels, int32_t* h_ncompo
 int gm_run_betweenness(gm_graph_t* g, const int32_t* h_sources, int32_t nsources,
                        double* d_bc, int32_t* d_last_depth, double* d_last_sigma, gm_stream_t stream);
 
+/* Minimum spanning forest by Boruvka rounds (gm_spanning_forest.hip) of the UNDIRECTED MULTIGRAPH under the edge list: directions
+ * do not matter, self-loops are ignored, parallel and antiparallel edges are separate candidates, so the lightest of them wins.
+ * A weight is the graph's 4-byte edge value read as SIGNED int32; a graph built without values weighs every edge 1 (the result is
+ * then a spanning forest and *h_total == *h_nedges); an edge-value width other than 4 is refused.  The result has nvertices -
+ * (number of weakly connected components) edges, spans every weakly connected component and has the minimum total weight.
+ * d_edges: int32 [nrows][3] in device order, overwritten: the row of the device slot that was hooked through an edge holds that
+ * edge as (u, v, w) -- 1-based vertex ids, u < v, w the weight of an input edge between u and v --, every other row (0, 0, 0) (a
+ * slot is hooked at most once in a call, so there is no compaction and no atomic placement).  *h_nedges = the number of such
+ * rows, *h_total = the int64 sum of their weights.  Ties between equal weights are broken by the entry's position in the adjacency
+ * that is read (GM_DIR_OUT when the graph has it, else GM_DIR_IN): with distinct weights the forest is unique and the same for
+ * every layout; with ties only the total and the sorted list of weights are (they are invariants of every minimum spanning
+ * forest).  Two calls on one graph object return the same bytes.  Refused before any GPU work, outputs untouched: shards, row
+ * ranges and graphs with an exchange callback (GM_ERR_UNSUPPORTED, "whole graphs only"), null pointers (GM_ERR_INVALID), an
+ * edge-value width other than 4 and nnz >= 2^32 - 1 (GM_ERR_UNSUPPORTED: the key of an entry holds its 32-bit position).
+ * Rounds: every tree picks its lightest leaving entry (a 64-bit atomic minimum of (weight, position) per entry and end), roots
+ * hook, every vertex jumps to its root; at most floor(log2(nvertices)) pick passes find work, whatever the diameter.
+ * gm_graph_last_stats afterwards: iterations = pick passes launched (the last, empty one included), spmv_launches = jump passes;
+ * send_ms = set-up (init + the row of every edge), spmv_ms = the rounds, apply_ms = the output.  The call returns after the stream
+ * has finished.  Option "msf_form": see gm_set_option. */
+int gm_run_spanning_forest(gm_graph_t* g, int32_t* d_edges /* [rows][3] */, int32_t* h_nedges, int64_t* h_total, gm_stream_t stream);
+
 /* runtime options.  "force_ordered" (0/1): run PageRank with the plain serial long-row fold
  * instead of the exact parallel replay (A/B check; results are bit-identical).  Graph-build experiments (read when a
  * graph is created): "short_row", "giant_row", "rank_by", "rank_cap", "col_tiles", "tile_min_row", "long_mid" (wave rows
@@ -713,7 +734,10 @@ int gm_run_betweenness(gm_graph_t* g, const int32_t* h_sources, int32_t nsources
  * form's -- the reference's -- bits by up to ~1e-5 of the vectors' scale, outside the 1e-6 bar; slower as well);
  * "lda_tile" (16 / 32 / 64: edges per step of the dedicated LDA multiply kernel, a measurement knob; results do not depend on it);
  * "tc_form" (triangle counting, a measurement knob as well: 0 = rows are dealt to the two count kernels automatically, the default;
- * 1 = every row whose own list fits a wave's LDS share goes to the row kernel; 2 = every row goes to the pieces kernel).
+ * 1 = every row whose own list fits a wave's LDS share goes to the row kernel; 2 = every row goes to the pieces kernel);
+ * "msf_form" (minimum spanning forest, a measurement knob as well, 0..11, default 0; results do not depend on it: bit 0 = no look
+ * before the 64-bit atomic minimum, bit 1 = the lanes of a wave that share a root do not combine their keys first, bits 2-3 = the jump
+ * pass follows 32 parents (0), one parent (pointer doubling: 4) or as many as it takes (one pass per round: 8)).
  * Every field of gm_engine_options_t below is also a key: gm_set_option then sets the PROCESS default, which a graph
  * uses unless gm_graph_set_option gave it a value of its own; the environment variable GRAPHMAT_OPTIONS="key=value,..."
  * sets such defaults for applications that cannot call this themselves (the reference's unchanged sources). */
@@ -884,9 +908,16 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
  *                            depth, of the current source
  *  21   GM_WS_BC_FLAG        betweenness: entries of the order      64                                 gm_betweenness.hip                    no
  *                            array and long rows so far
+ *  19   GM_WS_MSF_EDGE_ROWS  spanning forest: the row of every      nnz * 4 + 64                       gm_spanning_forest.hip                no
+ *                            CSR position
+ *  20   GM_WS_MSF_STATE      spanning forest: best (uint64), comp,  n * 20 + 320                       gm_spanning_forest.hip                no
+ *                            hook and edge_of per device slot
+ *  21   GM_WS_MSF_FLAG       spanning forest: the last pick pass    64                                 gm_spanning_forest.hip                no
+ *                            that found work, the last unfinished
+ *                            jump pass, edges, total
  *
- * Slots 19-21: gm_run_triangle_count, gm_run_connected_components, gm_run_kcore, gm_run_strong_components and gm_run_betweenness
- * are five separate calls, none runs inside another, and none keeps anything in these slots from one call to the next (each writes everything it
+ * Slots 19-21: gm_run_triangle_count, gm_run_connected_components, gm_run_kcore, gm_run_strong_components, gm_run_betweenness and
+ * gm_run_spanning_forest are six separate calls, none runs inside another, and none keeps anything in these slots from one call to the next (each writes everything it
  * reads there, every call), so their uses never live in one run; like all runs on one graph, the calls follow each other on one
  * stream.
  * Slot 6: no two of its uses are live in one run.  Top-down steps (GM_WS_PUSH_BIDS) exist only for a=b programs and
@@ -933,6 +964,9 @@ int gm_graph_last_stats(const gm_graph_t* g, gm_run_stats_t* out);
 #define GM_WS_BC_ORDER 19
 #define GM_WS_BC_STATE 20
 #define GM_WS_BC_FLAG 21
+#define GM_WS_MSF_EDGE_ROWS 19
+#define GM_WS_MSF_STATE 20
+#define GM_WS_MSF_FLAG 21
 int gm_graph_workspace(gm_graph_t* g, int slot, size_t bytes, void** d_ptr);
 /* Let the caller provide a scratch slot (e.g. a torch tensor it also hands to its collective
  * library): GM_WS_X = message values x (nvertices * elt bytes), GM_WS_XBITS = x presence bits
